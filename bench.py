@@ -1,8 +1,11 @@
 """bench.py -- Eulerian-calibration frames/sec on a 1080p x 256 buffer (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config P|Q|R] [--mode streams|sharded]
+    python bench.py --gpus N --steps K --warmup W [--config P|Q|R] [--mode streams|sharded] [--dump-outputs DIR] [--full]
 
-One step = one locate() (calibration + ROI) over one [T,H,W] frame buffer already resident in HBM.
+One step = one locate() (calibration + ROI) over one [T,H,W] frame buffer already resident in HBM.  A plain run sets up,
+warms up, times the K steps and prints the line; `ms_per_step` is the wall time of one timed step.  --dump-outputs DIR
+writes what the last timed step returned to its caller (locate()'s ROI) as DIR/roi.npy; the inputs are seeded, so two
+runs with the same arguments compute on the same frames.  --full adds everything else the line can carry (see below).
 N>1: one process per GPU.  When the script is started WITHOUT a launcher (`python bench.py --gpus 8`, WORLD_SIZE unset) it
 re-executes itself through `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`; started
 by the launcher (RANK / LOCAL_RANK / WORLD_SIZE in the environment) it is one rank of that job.  Default mode "streams"
@@ -10,9 +13,12 @@ by the launcher (RANK / LOCAL_RANK / WORLD_SIZE in the environment) it is one ra
 [H,W] heatmaps per step (an all-gather of sparse packets; dense all-reduce(sum) as the fallback).  --mode sharded: ONE
 buffer split by frame index over the GPUs (Mode A, strong scaling).  Rank 0 prints ONE JSON line.
 
-The default single-GPU P line also carries `configs`: summaries of BASELINE configs 2 (Q), 5 (R), 3 (F: LK on a 256x256 ROI with
-1000 points) and of P with a float32 frame buffer, each measured in the same process after the headline and checked against the
-CPU oracle (--no-configs skips them).
+With --full the single-GPU line also carries the measurements beside the headline, each in the same process after the timed
+steps: four more batches of K steps, the pipelined form, the per-phase breakdown, the host timeline, the uint8 / BGR frame
+buffers, the ROI flow, the data-dependence and worst-case streams, the CPU oracle's figure (`cpu_baseline`) and, for P,
+`configs`: summaries of BASELINE configs 2 (Q), 5 (R), 3 (F: LK on a 256x256 ROI with 1000 points) and of P with a float32
+frame buffer, each checked against the CPU oracle (the --no-* options below skip single parts of it).  N>1 with --full also
+times one stream without the exchange (`single_stream_same_run`).
 
 --config picks the workload (SURVEY 8 sizes):  P = 256 x 1080p, L=9, S=4, float64 buffer (the metric's own configuration,
 default);  Q = 128 x 720p, L=4, S=2, float64 (BASELINE config 2);  R = 512 x 4K, L=6, S=2, float16 buffer (config 5).
@@ -83,7 +89,13 @@ def parse():
     ap.add_argument("--stage-timeout", type=float, default=600.0, help="N>1: rank 0 prints an error line and ends the job when a stage "
                     "before the timed loop (rendezvous, communicator, first step, ...) makes no progress for this many seconds (0 = never)")
     ap.add_argument("--cpu-workers", type=int, default=-1, help="threads of the all-cores CPU figure (0 = skip, -1 = min(64, host cores))")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beside the headline as well (see the module "
+                    "docstring); without it a run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one returned "
+                    "(locate()'s ROI x, y, w, h) as DIR/roi.npy, float64; shape (0,) when no contour was found")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     T, H, W, L, S, dt = CONFIGS[a.config]
     a.frames = a.frames or T
     a.height = a.height or H
@@ -161,7 +173,8 @@ class RankReporter:
 
     @staticmethod
     def directory(port):
-        return os.path.join(os.environ.get("TMPDIR", "/tmp"), "respmon_bench_%s" % port)
+        # per user: the directories stay behind, and another user's one for the same port would not be writable
+        return os.path.join(os.environ.get("TMPDIR", "/tmp"), "respmon_bench_%d_%s" % (os.getuid(), port))
 
     @classmethod
     def collect(cls, port, world):
@@ -308,6 +321,13 @@ def cpu_baseline(vid_u8, n_frames, levels, skip, in_dtype, workers):
         dtm = time.perf_counter() - t0
         out["all_cores"] = {"value": n_frames / dtm, "unit": "frames/s", "cores": nw, "seconds": dtm, "roi_equals_single_thread": roi_mt == roi}
     return out
+
+
+def dump_outputs(out_dir, roi):
+    """--dump-outputs: what the caller of the timed path received from its last step, locate()'s ROI (x, y, w, h), as
+    out_dir/roi.npy in float64; shape (0,) when locate() found no contour and returned None."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "roi.npy"), np.asarray([] if roi is None else list(roi), dtype=np.float64))
 
 
 def library_kernel_stamp():
@@ -574,7 +594,7 @@ def run(a, rep):
     for _ in range(a.warmup):
         roi = step()
     single_ms = None
-    if world > 1 and not sharded:
+    if world > 1 and not sharded and a.full:
         # what ONE stream does on this GPU without any exchange, measured in the same run (every rank at once, rank 0 reports): the
         # N = 1 figure the scaling of `value` can be read against
         barrier()
@@ -592,6 +612,8 @@ def run(a, rep):
         roi = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:    # (the --full passes below run more steps and reassign `roi`)
+        dump_outputs(a.dump_outputs, roi)
     rep.stage("report")
     ms = (ctypes.c_double * 4)()
     ncalls = ctypes.c_int()
@@ -599,7 +621,7 @@ def run(a, rep):
     k_ms_total, k_calls = ms[0], ncalls.value     # frame-buffer kernel, HIP events inside the timed region
     # box noise made visible in one run: four more batches of --steps (`value` stays the first batch above)
     batch_ms = [elapsed / a.steps * 1e3]
-    if world == 1 and not a.no_batches:
+    if world == 1 and a.full and not a.no_batches:
         for _ in range(4):
             barrier()
             tb = time.perf_counter()
@@ -612,7 +634,7 @@ def run(a, rep):
     # so its frame-buffer kernel runs where the synchronous step leaves the GPU idle (host wait + contour stage + launch latency).
     # EXTRA key only -- `value` is the synchronous step above
     pipelined = None
-    if world == 1 and not a.no_batches:
+    if world == 1 and a.full and not a.no_batches:
         _capi.check(lib, lib.rm_profile_enable(ctx, 0), "rm_profile_enable")
         def pipe(n):
             rois_equal = True
@@ -654,20 +676,22 @@ def run(a, rep):
     contour_stage = {"components": cn.value,
                      "path": "device labelling + host border following of the candidates" if cl.value else "host border following"}
     # phase breakdown: separate untimed pass (bracketing every phase costs ~10 us of stream idle time each)
-    _capi.check(lib, lib.rm_profile_enable(ctx, 2), "rm_profile_enable")
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    _capi.check(lib, lib.rm_profile_read(ctx, ms, ctypes.byref(ncalls)), "rm_profile_read")
+    phases = None
+    if a.full:
+        _capi.check(lib, lib.rm_profile_enable(ctx, 2), "rm_profile_enable")
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        _capi.check(lib, lib.rm_profile_read(ctx, ms, ctypes.byref(ncalls)), "rm_profile_read")
+        phases = {"frame_buffer_kernel": ms[0] / max(ncalls.value, 1), "pyramid_rest_and_temporal": ms[1] / max(ncalls.value, 1),
+                  "collapse_passes": ms[2] / max(ncalls.value, 1), "heatmap_to_roi": ms[3] / max(ncalls.value, 1)}
     _capi.check(lib, lib.rm_profile_enable(ctx, 0), "rm_profile_enable")
-    phases = {"frame_buffer_kernel": ms[0] / max(ncalls.value, 1), "pyramid_rest_and_temporal": ms[1] / max(ncalls.value, 1),
-              "collapse_passes": ms[2] / max(ncalls.value, 1), "heatmap_to_roi": ms[3] / max(ncalls.value, 1)}
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax[0])
 
-    extras = world == 1 and not a.no_extras
+    extras = world == 1 and a.full and not a.no_extras
     n_extra = max(3, min(a.steps, 20))
     # where the host time of a synchronous step goes (include/respmon_hip_debug.h rm_debug_host_timeline): medians over a separate
     # batch of steps -- the read-out itself costs ~1 us per step, so it stays out of the timed region
@@ -1017,7 +1041,7 @@ def run(a, rep):
             "worst_case": worst,
             "configs": other,
         }
-        if world == 1 and a.cpu_frames != 0:
+        if world == 1 and a.full and a.cpu_frames != 0:
             n_cpu = a.cpu_frames
             if n_cpu < 0:
                 import psutil

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +30,7 @@ def _json_line(out):
 
 
 def test_bench_single_gpu_contract_line():
-    j = _json_line(_run(["--steps", "5", "--warmup", "2"] + SMALL + ["--cpu-frames", "16", "--cpu-workers", "4"]))
+    j = _json_line(_run(["--steps", "5", "--warmup", "2", "--full"] + SMALL + ["--cpu-frames", "16", "--cpu-workers", "4"]))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in j, k
@@ -48,6 +49,28 @@ def test_bench_single_gpu_contract_line():
     assert len(j["ms_per_step_batches"]["batches"]) == 5 and j["ms_per_step_batches"]["batches"][0] == j["ms_per_step"]
     w = j["worst_case"]
     assert w["noise"]["roi_equals_oracle"] and w["blobs16"]["roi_equals_oracle"] and w["slowest_vs_headline"] >= 1.0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full: the headline only (no extra passes), and --dump-outputs writes the ROI of the last timed step; the same
+    arguments give the same outputs."""
+    rois = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        j = _json_line(_run(["--steps", "7", "--warmup", "2", "--dump-outputs", str(d)] + SMALL))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in j, key
+        assert j["steps"] == 7 and j["higher_is_better"] is True and j["dtype"] == "f64" and j["unit"] == "frames/s"
+        assert abs(j["value"] - 64 / j["ms_per_step"] * 1e3) <= 1e-9 * j["value"]
+        assert j["ms_per_step_batches"]["batches"] == [j["ms_per_step"]]
+        for key in ("pipelined", "phases_ms_per_step", "alt_uint8_buffer", "roi_flow", "no_prune", "dense_stream", "host_timeline_us",
+                    "worst_case", "configs", "cpu_baseline"):
+            assert j[key] is None, key
+        assert sorted(os.listdir(d)) == ["roi.npy"]
+        roi = np.load(d / "roi.npy")
+        assert roi.dtype == np.float64 and roi.tolist() == [float(v) for v in j["roi"]]
+        rois.append(roi)
+    assert np.array_equal(rois[0], rois[1])
 
 
 @pytest.mark.parametrize("mode", ["streams", "sharded"])

@@ -179,11 +179,16 @@ def test_tools_and_peaks(golden):
 def test_bench_presets(monkeypatch):
     """bench.py host logic that needs no GPU: the --config presets (SURVEY 8 sizes P / Q / R) and explicit flags overriding them."""
     import sys
+    import pytest
     import bench
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse()
     assert (a.gpus, a.config, a.frames, a.height, a.width, a.levels, a.skip, a.in_dtype) == (1, "P", 256, 1080, 1920, 9, 4, "f64")
     assert a.steps * 1.0e-3 >= 0.08         # ~0.8 ms per step: the default timed region is about 0.1 s
+    assert a.full is False and a.dump_outputs is None      # a plain run measures the headline only and writes nothing
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
     monkeypatch.setattr(sys, "argv", ["bench.py", "--config", "Q"])
     a = bench.parse()
     assert (a.frames, a.height, a.width, a.levels, a.skip, a.in_dtype) == (128, 720, 1280, 4, 2, "f64")

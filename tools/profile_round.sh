@@ -24,9 +24,9 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 BENCH="python bench.py --steps $STEPS --warmup 5 $ARGS"
 if [ "$CFG" = "P" ]; then
-  timeout 900 $BENCH > $OUT/bench_n1.json 2> $OUT/bench_n1.err < /dev/null
+  timeout 900 $BENCH --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err < /dev/null
 else
-  timeout 900 $BENCH --no-extras > $OUT/bench_n1.json 2> $OUT/bench_n1.err < /dev/null
+  timeout 900 $BENCH --full --no-extras > $OUT/bench_n1.json 2> $OUT/bench_n1.err < /dev/null
 fi
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o k -- $BENCH --cpu-frames 0 --no-extras --no-batches > $OUT/bench_under_rocprof.json 2> $OUT/rocprof_stats.err < /dev/null
 PSTEPS=20; [ "$CFG" = "R" ] && PSTEPS=6

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout 2400 python -m pytest tests/ -q -m gpu > $OUT/pytest_gpu.log 2>&1
 tail -4 $OUT/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" >> $OUT/pytest_gpu.log 2>&1; tail -2 $OUT/pytest_gpu.log
-timeout 1200 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 1200 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 python - <<PY
 import json
 j = json.load(open("$OUT/bench_n1.json"))

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 timeout 2400 python -m pytest tests/ -x -q -m gpu > $OUT/pytest_gpu.log 2>&1
 tail -6 $OUT/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -3 $OUT/smoke.log
-timeout 1200 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err; python - <<PY
+timeout 1200 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err; python - <<PY
 import json
 j = json.load(open("$OUT/bench_n1.json"))
 print("ms_per_step", j["ms_per_step"], "frac", j["roofline"]["frac"], "kernel_ms", j["roofline"]["kernel_ms"], "traffic", j["roofline"]["traffic"], j["roofline"].get("traffic_stale"))
