@@ -456,6 +456,41 @@ RM_KERNEL __launch_bounds__(256) void k_frame_bounds_l1f(const double *cS, Chain
         if (who0 && hit0) { sm_mn = f64_min(sm_mn, v0); sm_mx = f64_max(sm_mx, v0); }
         if (who1 && hit1) { sm_mn = f64_min(sm_mn, v1); sm_mx = f64_max(sm_mx, v1); }
     }
+    // Float32 range.  The margin argument above holds while every float32 intermediate is finite: level-1 sums reach 64 M, and C_2
+    // itself may not fit a float.  A wave that met a |C_2| beyond 2^100 (FLT_MAX / 64 is ~2^122) writes its tiles' bounds again, in
+    // float64, from the extrema of their LEVEL-2 footprints -- rows 4 ty - 1 .. 4 ty + 5 by the columns of lanes 16 t - 1 .. 16 t + 17
+    // (clamped), every level-1 value of the footprint being a convex combination of those: looser, sound, finite.  Ordinary magnitudes
+    // never come here; the bounds in the state are then those of the rewritten bounds.
+    {
+        const float am = bl1_maxf(__builtin_fabsf(t_mn), __builtin_fabsf(t_mx));
+        if (__ballot(!(am <= 0x1p100f)) != 0ull) {   // (uniform)
+            const bool writer = lane < BL1_COLS && (lane & 15) == 15 && BL1_TILES * c + (lane >> 4) < ntx;
+            lo_mn = inf; lo_mx = -inf; hi_mn = inf; hi_mx = -inf;
+            for (int ty = ty_first; ty <= ty_last; ++ty) {
+                double mn = inf, mx = -inf;
+                const int ra = max(4 * ty - 1, 0), rb = min(4 * ty + 5, h2 - 1);
+                for (int i = ra; i <= rb; ++i) { const double v = *row_ptr(i); mn = f64_min(mn, v); mx = f64_max(mx, v); }
+                // the columns of both neighbours (this lane's taps), then the 17 lanes of each tile into its last lane (finalize()'s fold)
+                mn = f64_min(mn, f64_min(bl1_rot<0x13C>(mn), bl1_rot<0x134>(mn)));
+                mx = f64_max(mx, f64_max(bl1_rot<0x13C>(mx), bl1_rot<0x134>(mx)));
+                const double r_mn = bl1_rot<0x134>(mn), r_mx = bl1_rot<0x134>(mx);
+                if ((lane & 15) == 15) { mn = f64_min(mn, r_mn); mx = f64_max(mx, r_mx); }
+#define RM_BL1_FOLD(CTRL)                                                             \
+                {                                                                        \
+                    const double a_ = dpp_get<CTRL, 0xF>(mn), b_ = dpp_get<CTRL, 0xF>(mx); \
+                    mn = f64_min(mn, a_); mx = f64_max(mx, b_);                          \
+                }
+                RM_BL1_FOLD(0x111) RM_BL1_FOLD(0x112) RM_BL1_FOLD(0x114) RM_BL1_FOLD(0x118)
+#undef RM_BL1_FOLD
+                if (writer) {
+                    const size_t o = (size_t)u * ntiles + (size_t)ty * ntx + BL1_TILES * c + (lane >> 4);
+                    lo[o] = mn; hi[o] = mx;   // (the same lane wrote the float32 bounds there: its stores land in order)
+                    lo_mn = f64_min(lo_mn, mn); lo_mx = f64_max(lo_mx, mn);
+                    hi_mn = f64_min(hi_mn, mx); hi_mx = f64_max(hi_mx, mx);
+                }
+            }
+        }
+    }
     lo_mn = wave_min(lo_mn); lo_mx = wave_max(lo_mx); hi_mn = wave_min(hi_mn); hi_mx = wave_max(hi_mx);
     if (lane == 0 && lo_mn <= lo_mx) {
         const unsigned long long k_lo_mx = f64_key(lo_mx), k_lo_mn = f64_key(lo_mn), k_hi_mx = f64_key(hi_mx), k_hi_mn = f64_key(hi_mn);

@@ -71,6 +71,7 @@ int collapse_eval(rm_ctx *ctx, const SmallLevels &sl, int T, int t0, int t1, dou
 {
     CollapseState *st = ctx->d_state;
     cp.valid = false;
+    cp.l1_bounds = false;   // (set below when this call's bounds are the level-1 extrema; the plan outlives the call)
     cp.cS = sl.cS; cp.T = T; cp.t0 = t0; cp.t1 = t1; cp.H = sl.h[0]; cp.W = sl.w[0]; cp.S = sl.S;
     const size_t npix = (size_t)cp.H * cp.W;
     const int Th = sym_frames(T);   // C_S, the bounds and the pairs exist for the unique frames only (rm_kernels.h sym_frame)
@@ -133,6 +134,7 @@ int collapse_eval(rm_ctx *ctx, const SmallLevels &sl, int T, int t0, int t1, dou
     RM_TRY(ws(ctx, "heavy_tiles", (size_t)ntiles, &cp.heavy));
     cp.xs_tab = nullptr;
     if (ctx->dbg.xs && tile_eval_ok(g) && !cp.fused) RM_TRY(ws(ctx, "xs_tab", (size_t)npairs, &cp.xs_tab));   // exception store (rm_xstore.h): one entry per pair
+    ctx->dbg_cS = sl.cS; ctx->dbg_cS_bytes = sizeof(double) * (size_t)Th * g.h[g.S] * g.w[g.S];   // (after this call's last ws(): rm_debug_workspace "cS")
     if (!sl.bounds_ready) {
         // per-frame separable form, in bands of tile rows whose row-extrema table fits 64 KB of LDS; the per-pair kernel
         // remains for geometries where even one tile row does not fit
@@ -160,7 +162,6 @@ int collapse_eval(rm_ctx *ctx, const SmallLevels &sl, int T, int t0, int t1, dou
         while (band > 4 && (long long)Th * ((g.tiles_y + band - 1) / band) < 1024) band = (band + 1) / 2;
         const int tbl_rows = tbl_rows_of(band);
         const size_t tbl = (size_t)tbl_rows * row_bytes;
-        cp.l1_bounds = false;
         if (ctx->dbg.bounds_l1 && bounds_l1_ok(g) && ntiles < (1 << 24)) {
             cp.l1_bounds = true;
             // skip 2: the extrema of the LEVEL-1 footprints, streaming (rm_bounds_l1.h) -- a wave per three tile columns and band of tile rows

@@ -25,6 +25,8 @@ int ws_get(rm_ctx *ctx, const std::string &name, size_t bytes, void **out)
             // kernels of a submission nobody has fetched yet may still hold the old pointer: wait for them, then free
             for (LocateTicket &t : ctx->tickets)
                 if (t.active && t.done) HIP_TRY(hipEventSynchronize(t.done));
+            const char *c = (const char *)ctx->dbg_cS, *p0 = (const char *)b.p;
+            if (c && c >= p0 && c < p0 + b.cap) ctx->dbg_cS = nullptr;   // (the last collapse's level lived in this buffer)
             HIP_TRY(hipFree(b.p));
         }
         b.p = nullptr; b.cap = 0;
@@ -208,12 +210,20 @@ extern "C" const char *rm_debug_kernel_source_stamp(void) { return RM_FRAME_KERN
 extern "C" int rm_debug_workspace(rm_ctx *ctx, const char *name, void *out_host, size_t bytes, void *stream)
 {
     if (!ctx || !name || !out_host) return fail(RM_E_BADARG, "rm_debug_workspace: bad argument");
-    auto it = ctx->bufs.find(name);
-    if (it == ctx->bufs.end() || !it->second.p) return fail(RM_E_BADARG, "rm_debug_workspace: no workspace buffer '%s'", name);
-    if (bytes > it->second.cap) return fail(RM_E_BADARG, "rm_debug_workspace: '%s' holds %zu bytes, %zu asked for", name, it->second.cap, bytes);
+    const void *src = nullptr;
+    size_t cap = 0;
+    if (!strcmp(name, "cS")) {   // the level the last collapse read, wherever it lives (a single filtered level is bp_all itself)
+        if (!ctx->dbg_cS) return fail(RM_E_BADARG, "rm_debug_workspace: no collapsed level since the last collapse (or its buffer was reallocated)");
+        src = ctx->dbg_cS; cap = ctx->dbg_cS_bytes;
+    } else {
+        auto it = ctx->bufs.find(name);
+        if (it == ctx->bufs.end() || !it->second.p) return fail(RM_E_BADARG, "rm_debug_workspace: no workspace buffer '%s'", name);
+        src = it->second.p; cap = it->second.cap;
+    }
+    if (bytes > cap) return fail(RM_E_BADARG, "rm_debug_workspace: '%s' holds %zu bytes, %zu asked for", name, cap, bytes);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(out_host, it->second.p, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_host, src, bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(stream_wait(s));
     return RM_OK;
 }

@@ -533,19 +533,21 @@ __global__ __launch_bounds__(64) void k_dense_sum_w(const double *cS, ChainGeom 
     }
     // ---- level 2 -> 1: lane c < 34 owns level-1 column xv1 + c
     double hw_a = 0.0, hw_b = 0.0, hw_c = 0.0;
-    int h_base = 0;
+    int h_base = 0, ha_off = 0;   // tap a of staged row q at h_base + ha_off + q P2
     if (S == 2) {
         const int sw2 = g.w[2];
-        const int xv = xv1 + (lane < P1 ? lane : 0);
-        if (lane < P1 && xv >= 0 && xv < sw1) {
+        // a level-1 column outside the image takes the value of the nearest column inside it: the level-0 taps that read it have
+        // weight zero, and 0 * a finite value is zero where 0 * inf or 0 * NaN would not be
+        const int xv = min(max(xv1 + (lane < P1 ? lane : 0), 0), sw1 - 1);
+        if (lane < P1) {
             const int j = xv >> 1;
             const bool left = j == 0, right = j == sw2 - 1;
-            if (xv & 1) { hw_b = right ? 8.0 : 4.0; hw_c = right ? 0.0 : 4.0; }
+            if (xv & 1) { hw_b = right ? 8.0 : 4.0; hw_c = right ? 0.0 : 4.0; ha_off = 1; }   // (weight-zero tap a reads b: make_htap()'s ia = j)
             else { hw_a = left ? 0.0 : 1.0; hw_b = right ? 7.0 : 6.0; hw_c = left ? 2.0 : (right ? 0.0 : 1.0); }
         }
         // taps j - 1, j, j + 1 of staged row q sit at h_base + q P2 + {0, 1, 2}: virtual column (xv >> 1) - 1 - (16 tx - 2)
         h_base = ((xv >> 1) - 1) - (16 * tx - 2);
-        h_base = min(max(h_base, 0), P2 - 3);   // (lanes >= 34 and out-of-image columns: any valid address, weights are zero)
+        h_base = min(max(h_base, 0), P2 - 3);   // (lanes >= 34: any valid address, weights are zero)
     }
     // ---- level 1 -> 0: lane = (column pair cp, row half rh): columns X, X + 1, rows Y0 .. Y0 + 7
     const int cp = lane & 31, rh = lane >> 5;
@@ -592,7 +594,7 @@ __global__ __launch_bounds__(64) void k_dense_sum_w(const double *cS, ChainGeom 
 #pragma unroll
                     for (int q = 0; q < R2; ++q) {
                         const double *row = sl + h_base + q * P2;
-                        hq[q] = dw_tap3(row[0], row[1], row[2], hw_a, hw_b, hw_c);
+                        hq[q] = dw_tap3(row[ha_off], row[1], row[2], hw_a, hw_b, hw_c);
                     }
                     // level-1 rows p = 0 .. 9 <-> virtual rows 8 ty - 1 + p: p even is an odd row (values of level-2 rows 4 ty - 1 + p / 2
                     // and the next one), p odd an even row (the three rows around 4 ty + (p - 1) / 2); hq[q] <-> level-2 row 4 ty - 1 + q
@@ -713,13 +715,14 @@ __global__ __launch_bounds__(64 * NW) void k_dense_sum_wf(const double *cS, Chai
     {
         const int Th = sym_frames(T);
         const double margin = st->margin;
+        const bool prune = lo != nullptr && __builtin_isfinite(top + margin) && __builtin_isfinite(margin);   // (a threshold that is not finite prunes nothing)
         for (int c0 = t_first; c0 < t_end; c0 += 64 * NW) {
             const int t = c0 + (int)threadIdx.x;
             bool kept = t < t_end;
             if (kept && slot_of) {
                 const int u = sym_frame(t, T);
                 kept = slot_of[slot_index(u, tile, Th)] != SLOT_PRUNED;
-                if (kept && lo) kept = !(lo[(size_t)u * ntiles_ + tile] - margin >= top);   // (a NaN bound keeps the pair: NaN must reach the sum)
+                if (kept && prune) kept = !(lo[(size_t)u * ntiles_ + tile] - margin >= top);   // (a NaN bound keeps the pair: NaN must reach the sum)
             }
             const unsigned long long mk = __ballot(kept);
             if (lane == 0) s_wcnt[wave] = __popcll(mk);
@@ -744,14 +747,16 @@ __global__ __launch_bounds__(64 * NW) void k_dense_sum_wf(const double *cS, Chai
         off_l[p] = i < G::NST ? i : -1;
     }
     double hw_a = 0.0, hw_b = 0.0, hw_c = 0.0;
-    int h_base = 0;
+    int h_base = 0, ha_off = 0;   // tap a of staged row q at h_base + ha_off + q P2
     if (S == 2) {
         const int sw2 = g.w[2];
-        const int xv = xv1 + (lane < P1 ? lane : 0);
-        if (lane < P1 && xv >= 0 && xv < sw1) {
+        // a level-1 column outside the image takes the value of the nearest column inside it: the level-0 taps that read it have
+        // weight zero, and 0 * a finite value is zero where 0 * inf or 0 * NaN would not be
+        const int xv = min(max(xv1 + (lane < P1 ? lane : 0), 0), sw1 - 1);
+        if (lane < P1) {
             const int j = xv >> 1;
             const bool left = j == 0, right = j == sw2 - 1;
-            if (xv & 1) { hw_b = right ? 8.0 : 4.0; hw_c = right ? 0.0 : 4.0; }
+            if (xv & 1) { hw_b = right ? 8.0 : 4.0; hw_c = right ? 0.0 : 4.0; ha_off = 1; }   // (weight-zero tap a reads b: make_htap()'s ia = j)
             else { hw_a = left ? 0.0 : 1.0; hw_b = right ? 7.0 : 6.0; hw_c = left ? 2.0 : (right ? 0.0 : 1.0); }
         }
         h_base = ((xv >> 1) - 1) - (16 * tx - 2);
@@ -795,7 +800,7 @@ __global__ __launch_bounds__(64 * NW) void k_dense_sum_wf(const double *cS, Chai
 #pragma unroll
                 for (int q = 0; q < R2; ++q) {
                     const double *row = sl + h_base + q * P2;
-                    hq[q] = dw_tap3(row[0], row[1], row[2], hw_a, hw_b, hw_c);
+                    hq[q] = dw_tap3(row[ha_off], row[1], row[2], hw_a, hw_b, hw_c);
                 }
                 double prev = 0.0;
 #pragma unroll

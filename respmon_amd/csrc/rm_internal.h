@@ -203,6 +203,7 @@ struct rm_ctx {
     int dense_hint = 0;             // the last rm_locate of this context met a dense selection (more than a quarter of the pairs kept)
     long long store_hint_slots = 0; // slots a selection of this context needed when it overflowed the value store (rm_locate grows the store to it)
     // measurement hook (rm_profile_*)
+    const double *dbg_cS = nullptr; size_t dbg_cS_bytes = 0;   // the collapsed level of the last collapse (rm_debug_workspace "cS": bp_all itself when L - 2 == S)
     long long dbg_pairs = 0, dbg_cap = 0, dbg_mine = 0; int dbg_mode = 0, dbg_auto_dense = 0, dbg_fused = 0;   // the SumPlan of the last collapse (host copy)
     int prof_mode = 0;                     // 0 off, 1 frame-buffer kernel only, 2 all phases
     bool prof_on = false;

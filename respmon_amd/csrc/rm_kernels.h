@@ -1685,7 +1685,15 @@ RM_KERNEL __launch_bounds__(256) void k_select_pairs(const double *lo, const dou
     }
     const double mx_ = ub_max + m, mn_ = ub_min + m;
     const double top_ub = (mx_ - (mx_ - mn_) * thr) + m;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { st->margin = m; st->top_ub = top_ub; }
+    // a threshold that is not finite (an infinite or NaN bound, or a value range that overflows float64) proves nothing: no pair is
+    // pruned on it -- the call is evaluated as with RM_FLAG_NO_PRUNE.  (The bounds kernels keep their bounds finite; this is the second
+    // line of defence: a bound kernel with that flaw costs speed, not correctness.)  The sums see the same verdict: a NaN top_ub and margin.
+    const bool thr_finite = __builtin_isfinite(m) && __builtin_isfinite(top_ub) && __builtin_isfinite(lb_max) && __builtin_isfinite(ub_min);
+    if (!thr_finite) no_prune = 1;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        st->margin = thr_finite ? m : __builtin_nan("");
+        st->top_ub = thr_finite ? top_ub : __builtin_nan("");
+    }
     unsigned int fC = 0, fD = 0;   // bit k: pair k is C / D
     unsigned long long cnt = 0;    // D | A << 20 | B << 40
 #pragma unroll
@@ -1911,7 +1919,7 @@ RM_KERNEL __launch_bounds__(64) void k_eval_pairs(const double *cS, ChainGeom g,
             pmn = wave_min(pmn);
             // nothing of this tile can fall below top (top <= top_ub): every pixel adds `min`, exactly like a pruned pair --
             // no values to park, and the sum pass never sees the frame
-            if (pmn >= top_ub) {
+            if (__builtin_isfinite(top_ub) && pmn >= top_ub) {
                 if (lane == 0) slot_of[slot_index(u, tile, Th)] = SLOT_PRUNED;
             } else if (x <= R0.x1) {
                 double *d = store + (size_t)slot * (CT_H * CT_W) + lane;

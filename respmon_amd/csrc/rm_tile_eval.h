@@ -329,7 +329,7 @@ __global__ __launch_bounds__(64) void k_eval_pairs_fast(const double *cS, ChainG
             pmn = wave_min(pmn);
             // nothing of this tile can fall below top (top <= top_ub): every pixel adds `min`, exactly like a pruned pair --
             // no values to park, and the sum pass never sees the frame
-            if (pmn >= top_ub) {
+            if (__builtin_isfinite(top_ub) && pmn >= top_ub) {
                 if (lane == 0) slot_of[slot_index(u, tile, Th)] = SLOT_PRUNED;
             } else {
                 // lane (column pair cp, row half rg): rows 8 rg .. 8 rg + 7 of the tile, columns 2 cp, 2 cp + 1: 16 bytes per row
@@ -789,12 +789,15 @@ __global__ __launch_bounds__(64) RM_WAVES_PER_EU_IF(S <= 2, 4, 3) void k_dense_s
     // its four waves balanced, measured 115.3 against 115.0 us and was dropped).  (tile-major slot_of: a few cache lines; lo is
     // [unique frame][tile].)
     const double margin = st->margin;
-    // (the exhaustive baseline and the developer switch evaluate every kept pair to the end: no level-1 minimum reaches +inf)
-    const double top_m = lo != nullptr ? top + margin : __builtin_huge_val();
+    // (the exhaustive baseline and the developer switch evaluate every kept pair to the end: no level-1 minimum reaches +inf; so does
+    //  a call whose top or margin is not finite -- k_select_pairs found no finite threshold, or the value range overflows float64)
+    const bool prune = lo != nullptr && __builtin_isfinite(top + margin) && __builtin_isfinite(margin);
+    const double top_m = prune ? top + margin : __builtin_huge_val();
+    if (!prune) l1_stop = 0;   // (nothing may stop at level 1 then: a tile of NaN has no level-1 minimum below +inf, and would add `min`)
     for (int c0 = 0; c0 < Th; c0 += 64) {
         const int u = c0 + lane;
         bool kept = u < Th && slot_of[slot_index(u, tile, Th)] != SLOT_PRUNED;
-        if (kept && lo) kept = !(lo[(size_t)u * ntiles + tile] - margin >= top);   // (a NaN bound keeps the pair: NaN must reach the sum)
+        if (kept && prune) kept = !(lo[(size_t)u * ntiles + tile] - margin >= top);   // (a NaN bound keeps the pair: NaN must reach the sum)
         const unsigned long long mk = __ballot(kept);
         if (lane == 0) s_mask[c0 >> 6] = mk;
     }

@@ -58,6 +58,7 @@ __global__ __launch_bounds__(64) void k_xs_eval(const double *cS, ChainGeom g, i
     const double min_val = f64_unkey(fold_min_keys(st->min_keys, st->min_key)), max_val = f64_unkey(fold_max_keys(st->max_keys, st->max_key));
     const double top = max_val - (max_val - min_val) * threshold;   // transforms.py:184-189
     const double margin = st->margin;
+    const bool prune = lo != nullptr && __builtin_isfinite(top + margin) && __builtin_isfinite(margin);   // (a threshold that is not finite prunes nothing)
     const size_t fs = (size_t)g.h[S] * g.w[S];
     const int H0 = g.h[0], W0 = g.w[0];
     // (uniform) this wave's chunk of the store: words [cur, end).  The first chunk of every wave is its own by position -- no atomic: the
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(64) void k_xs_eval(const double *cS, ChainGeom g, i
         if (kept) {
             const int u = (int)(my_idx / (unsigned)ntiles), tile = (int)(my_idx - (unsigned)u * (unsigned)ntiles);
             kept = slot_of[slot_index(u, tile, Th)] != SLOT_PRUNED;               // (a C pair that is not a D pair: evaluated for the extrema only)
-            if (kept && lo) kept = !(lo[my_idx] - margin >= top);                 // (a NaN bound keeps the pair: NaN must reach the sum)
+            if (kept && prune) kept = !(lo[my_idx] - margin >= top);                 // (a NaN bound keeps the pair: NaN must reach the sum)
         }
         unsigned long long todo = __ballot(kept);
         // the footprint of the NEXT kept pair travels while this one is evaluated

@@ -431,6 +431,11 @@ def main():
         if rng.random() < 0.5:    # the other knobs of locate(): band, amplification, mask width, binary threshold
             kw.update(freq_min=float(rng.uniform(0.05, 0.6)), freq_max=float(rng.uniform(0.7, 2.5)), amplification=float(rng.choice([1, 50, 500, 5000])),
                       temporal_threshold=float(rng.choice([0.0, 0.1, 0.5, 0.7, 0.9, 1.0, 1.3])), threshold=int(rng.choice([0, 5, 20, 60, 200, 254])))
+        # about one case in five: an amplification drawn log-uniformly over +-1e-300 .. 1e300, where float32 intermediates of the
+        # tile bounds overflow or underflow -- the heatmap must then also equal the exhaustive evaluation's bit for bit
+        extreme = rng.random() < 0.2
+        if extreme:
+            kw["amplification"] = float(rng.choice([-1.0, 1.0]) * 10.0 ** rng.uniform(-300.0, 300.0))
         ckw = {k: v for k, v in kw.items() if k != "threshold"}
         try:
             with np.errstate(all="ignore"):
@@ -453,6 +458,9 @@ def main():
             scale = max(np.abs(mid["avg_frame"]).max(), 1e-3 * float(kw.get("amplification", 500)) * float(np.abs(ref_in).max()), 1e-300)
             err = np.abs(heat - mid["avg_frame"]).max() / scale
             ok = got == ref and (err <= 1e-12 or not np.isfinite(scale))
+            if ok and extreme:
+                exhaustive = rdist.hip_calibrate(dev, fps, flags=(64 if reforder else 0) | 1, **ckw).cpu().numpy()
+                ok = np.array_equal(heat, exhaustive, equal_nan=True)
             err = float(err)
             if ok and S >= 1 and T >= 3:
                 world = int(rng.integers(1, 4))
