@@ -241,13 +241,15 @@ int rm_roi_to_uint8(rm_ctx *ctx, const void *frame_dev, int dtype, int H, int W,
 
 /* ---- base.py:365-366 cv2.goodFeaturesToTrack(img_u8, mask=None, maxCorners, qualityLevel,
  *      minDistance, blockSize).  pts_host: float32 (x,y) pairs, capacity max_corners; *n_host = count
- *      (0 <=> cv2 returns None). */
+ *      (0 <=> cv2 returns None; always 0 when h < 3 or w < 3). */
 int rm_good_features_to_track(rm_ctx *ctx, const uint8_t *img_dev, int h, int w, int max_corners,
                               double quality_level, double min_distance, int block_size,
                               float *pts_host, int *n_host, void *stream);
 
 /* ---- base.py:371-372 cv2.calcOpticalFlowPyrLK(prev, next, pts, None, winSize, maxLevel,
- *      criteria=(EPS|COUNT, max_count, epsilon)).  pts in/out: host float32 (x,y) pairs; status host u8. */
+ *      criteria=(EPS|COUNT, max_count, epsilon)).  pts in/out: host float32 (x,y) pairs; status host u8.
+ *      RM_E_UNSUPPORTED when win_w * win_h > 1024 or the pyramid, after OpenCV's clamping of maxLevel, needs more than
+ *      8 levels (also from rm_flow_step). */
 int rm_calc_optical_flow_pyr_lk(rm_ctx *ctx, const uint8_t *prev_dev, const uint8_t *next_dev, int h, int w,
                                 const float *pts_in_host, int npts, int win_w, int win_h, int max_level,
                                 int max_count, double epsilon, float *pts_out_host, uint8_t *status_host,

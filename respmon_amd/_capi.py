@@ -13,6 +13,7 @@ RM_SPARSE_FALLBACK = 2
 RM_COMM_ID_BYTES = 128
 RM_EXCHANGE_SPARSE, RM_EXCHANGE_DENSE = 1, 2
 RM_E_BADARG = -1
+RM_E_UNSUPPORTED = -4
 RM_E_COMM = -6
 RM_E_BUSY = -7
 RM_LOCATE_TICKETS = 2

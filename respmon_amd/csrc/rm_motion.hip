@@ -50,8 +50,11 @@ extern "C" int rm_roi_to_uint8(rm_ctx *ctx, const void *frame, int dtype, int H,
 extern "C" int rm_good_features_to_track(rm_ctx *ctx, const uint8_t *img, int h, int w, int max_corners, double quality,
                                          double min_distance, int block_size, float *pts, int *n, void *stream)
 {
-    if (!ctx || !img || !pts || !n || h < 3 || w < 3 || block_size < 1 || (block_size & 1) == 0)
+    if (!ctx || !img || !pts || !n || h < 1 || w < 1 || block_size < 1 || (block_size & 1) == 0)
         return fail(RM_E_BADARG, "rm_good_features_to_track: bad argument");
+    // the local-maximum test excludes the 1-pixel frame, so an image under 3 pixels in either direction has no corners
+    // (OpenCV: "no corners", base.py:367 then reports "No motion key points found.")
+    if (h < 3 || w < 3) { *n = 0; return RM_OK; }
     std::string err;
     int rc = flow_good_features(ctx->flow, img, h, w, max_corners, quality, min_distance, block_size, pts, n, (hipStream_t)stream, err);
     if (rc < 0) return fail(rc, "%s", err.c_str());
@@ -139,7 +142,7 @@ static int flow_state_crop(FlowState &fs, int side, uint8_t **crop)
 extern "C" int rm_flow_begin(rm_ctx *ctx, rm_flow_state *state, const void *frame, int dtype, int H, int W, int x, int y, int w, int h, int max_corners,
                              double quality, double min_distance, int block_size, float *pts_host, int *n_host, void *stream)
 {
-    if (!ctx || !state || !frame || !pts_host || !n_host || !valid_dtype(dtype) || !roi_ok(H, W, x, y, w, h) || h < 3 || w < 3 || block_size < 1 ||
+    if (!ctx || !state || !frame || !pts_host || !n_host || !valid_dtype(dtype) || !roi_ok(H, W, x, y, w, h) || block_size < 1 ||
         (block_size & 1) == 0)
         return fail(RM_E_BADARG, "rm_flow_begin: bad argument");
     if (state->device != ctx->device) return fail(RM_E_BADARG, "rm_flow_begin: the flow state belongs to device %d, the context to %d", state->device, ctx->device);
@@ -154,9 +157,12 @@ extern "C" int rm_flow_begin(rm_ctx *ctx, rm_flow_state *state, const void *fram
     RM_TRY(flow_state_pts(fs, &pa, &pb));
     RM_TRY(flow_crop(ctx, frame, dtype, H, W, x, y, w, h, crop, s));
     fs.pyr_levels[0] = 0;
-    std::string err;
-    int rc = flow_good_features(fs.ws, crop, h, w, max_corners, quality, min_distance, block_size, pts_host, n_host, s, err);
-    if (rc < 0) return fail(rc, "%s", err.c_str());
+    *n_host = 0;
+    if (h >= 3 && w >= 3) {   // (narrower crops have no corners: rm_good_features_to_track)
+        std::string err;
+        int rc = flow_good_features(fs.ws, crop, h, w, max_corners, quality, min_distance, block_size, pts_host, n_host, s, err);
+        if (rc < 0) return fail(rc, "%s", err.c_str());
+    }
     fs.npts = *n_host;
     if (*n_host > 0) {
         HIP_TRY(hipMemcpyAsync(pa, pts_host, sizeof(float) * 2 * (size_t)*n_host, hipMemcpyHostToDevice, s));

@@ -1,6 +1,7 @@
 """GPU parity of the ROI motion-extraction path (reference base.py:354-407): Shi-Tomasi corners, pyramidal LK,
 mean flow and PCA reduction against the CPU oracle.  Bit-exact corner coordinates / status; flow vectors within
-1e-4 relative (in practice identical: the kernels keep OpenCV's accumulation order)."""
+1e-4 relative (in practice identical: the kernels keep OpenCV's accumulation order).
+Crops from 1x1 up to whole 4K frames, > FLOW_FINISH_MAX points and exact-arithmetic PCA: tests/test_gpu_motion_edges.py."""
 import numpy as np
 import pytest
 

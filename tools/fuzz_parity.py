@@ -29,7 +29,7 @@ def fuzz_flow(budget, seed):
     t_end = time.time() + budget
     n = bad = 0
     while time.time() < t_end:
-        H = int(rng.integers(24, 260)); W = int(rng.integers(24, 260))
+        H = int(rng.integers(1, 260)); W = int(rng.integers(1, 260))
         render = synth.synth_texture(H, W, seed=int(rng.integers(1 << 30)), n_waves=int(rng.integers(3, 14)), n_spots=int(rng.integers(0, 50)))
         a = render(0.0, 0.0)
         b = render(float(rng.uniform(-3, 3)), float(rng.uniform(-3, 3)))
@@ -66,7 +66,7 @@ def fuzz_flow_lk(budget, seed):
     n = bad = 0
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
     while time.time() < t_end:
-        H = int(rng.integers(24, 200)); W = int(rng.integers(24, 200))
+        H = int(rng.integers(1, 200)); W = int(rng.integers(1, 200))
         render = synth.synth_texture(H, W, seed=int(rng.integers(1 << 30)))
         a = render(0.0, 0.0); b = render(float(rng.uniform(-2.5, 2.5)), float(rng.uniform(-2.5, 2.5)))
         npts = int(rng.integers(1, 60))
