@@ -285,6 +285,24 @@ int rm_flow_step(rm_ctx *ctx, rm_flow_state *state, const void *frame_dev, int d
                  int max_level, int max_count, double epsilon, float *mean_xy_host, int *n_good_host, void *stream);
 int rm_flow_points(rm_ctx *ctx, rm_flow_state *state, float *pts_host, int cap, int *n_host, void *stream);
 
+/* ---- extract_motion() over a whole clip that is resident on the device: frames_dev is [N,H,W], contiguous, of a frame dtype.
+ *      Each call waits for the stream once; the number of launches does not grow with N.
+ *      rm_roi_mean_clip: out_host[i] = rm_roi_mean of frame i, bit for bit.
+ *      rm_flow_clip = N successive rm_flow_step calls on a state rm_flow_begin has begun: mean_xy_host[N][2] and n_good_host[N] per
+ *        frame, the same error codes for the same arguments (with nothing launched), and the same state afterwards -- the last
+ *        crop, the surviving points packed in point order -- so rm_flow_step and rm_flow_clip calls may be mixed and a clip may be
+ *        split anywhere.  A state with no points left only advances its previous image (mean 0, n_good 0 for every frame).
+ *        Crops, pyramids and derivatives of all frames are built frame-parallel, one wavefront per point then walks the frames in
+ *        order; the clip is worked through in chunks whose workspace (about 6.7 bytes per ROI pixel and frame) stays under 256 MiB.
+ *      rm_pca_reduce_windows: for every j in [first, n), out_host[j - first] = rm_pca_reduce of rows max(0, j + 1 - window) .. j of
+ *        motion_host[n][2] (0.0 below two rows): the values extract_motion returns while the motion_data deque of base.py:473-475
+ *        holds at most `window` rows. */
+int rm_roi_mean_clip(rm_ctx *ctx, const void *frames_dev, int dtype, int N, int H, int W, int x, int y, int w, int h,
+                     double *out_host, void *stream);
+int rm_flow_clip(rm_ctx *ctx, rm_flow_state *state, const void *frames_dev, int dtype, int N, int H, int W, int x, int y, int w, int h,
+                 int win_w, int win_h, int max_level, int max_count, double epsilon, float *mean_xy_host, int *n_good_host, void *stream);
+int rm_pca_reduce_windows(rm_ctx *ctx, const float *motion_host, int n, int first, int window, double *out_host, void *stream);
+
 /* ---- multi-GPU steps with RCCL behind the C-ABI (the call site they replace is base.py:444, run once per GPU).
  *      One process per GPU, one context per process.  librccl is opened at run time (dlopen), so single-GPU users never need it.
  *        rm_comm_unique_id   rank 0 makes the id (RM_COMM_ID_BYTES bytes = ncclUniqueId) and hands it to the other ranks by any

@@ -91,6 +91,9 @@ SIGNATURES = {
     "rm_flow_points": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "rm_mean_flow": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "rm_pca_reduce": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "rm_roi_mean_clip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "rm_flow_clip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
+    "rm_pca_reduce_windows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "rm_bgr_to_gray": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "rm_comm_unique_id": (_i, [_vp]),
     "rm_comm_init": (_i, [_vp, _i, _i, _vp]),

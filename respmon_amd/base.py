@@ -259,6 +259,41 @@ class _Backend:
                                                      device.stream_ptr()), "rm_pca_reduce")
         return out.value
 
+    # -- a whole resident [N,H,W] clip per call: one host synchronisation each (include/respmon_hip.h) ------------------------
+    def roi_mean_clip(self, frames, x, y, w, h):
+        import ctypes
+        frames = frames.contiguous()
+        N, H, W = frames.shape
+        out = np.empty(N, dtype=np.float64)
+        _capi.check(self.lib, self.lib.rm_roi_mean_clip(device.ctx(), device.ptr(frames), device.dtype_code(frames), N, H, W, x, y, w, h,
+                                                        ctypes.c_void_p(out.ctypes.data), device.stream_ptr()), "rm_roi_mean_clip")
+        return out
+
+    def flow_clip(self, state, frames, x, y, w, h, winSize, maxLevel, criteria):
+        import ctypes
+        frames = frames.contiguous()
+        N, H, W = frames.shape
+        ctype, max_count, eps = criteria
+        if not (ctype & 1):
+            max_count = 30
+        if not (ctype & 2):
+            eps = 0.01
+        mean = np.empty((N, 2), dtype=np.float32)
+        ng = np.empty(N, dtype=np.int32)
+        _capi.check(self.lib, self.lib.rm_flow_clip(device.ctx(), state.handle, device.ptr(frames), device.dtype_code(frames), N, H, W, x, y, w, h,
+                                                    int(winSize[0]), int(winSize[1]), int(maxLevel), int(max_count), float(eps),
+                                                    ctypes.c_void_p(mean.ctypes.data), ctypes.c_void_p(ng.ctypes.data), device.stream_ptr()),
+                    "rm_flow_clip")
+        return mean, ng
+
+    def pca_reduce_windows(self, motion_data, first, window):
+        import ctypes
+        m = np.ascontiguousarray(motion_data, dtype=np.float32).reshape(-1, 2)
+        out = np.empty(len(m) - int(first), dtype=np.float64)
+        _capi.check(self.lib, self.lib.rm_pca_reduce_windows(device.ctx(), ctypes.c_void_p(m.ctypes.data), len(m), int(first), int(window),
+                                                             ctypes.c_void_p(out.ctypes.data), device.stream_ptr()), "rm_pca_reduce_windows")
+        return out
+
 
 class RespiratoryMonitor:
     CAP_PROP_FRAME_WIDTH, CAP_PROP_FRAME_HEIGHT, CAP_PROP_FPS = 3, 4, 5
@@ -607,9 +642,7 @@ class RespiratoryMonitor:
     def run(self):
         """base.py:409-513.  Frame accounting: frame 0 is consumed by 'initialize', the next
         T fill the buffer, one more triggers locate() and is dropped, measurement starts after that."""
-        for tag in ('Measurement Loop', 'Frame Capture', 'Calibration Measurement'):
-            if not self.benchmarker.has_tag(tag):
-                self.benchmarker.add_tag(tag)
+        self._add_benchmark_tags()
         while self.cap.isOpened():
             self.loop_start_time = time.time()
             self.benchmarker.tick_start('Frame Capture')
@@ -617,11 +650,142 @@ class RespiratoryMonitor:
             if isinstance(frame, bool):
                 break
             self.benchmarker.tick_end('Frame Capture')
-            self.step(frame)
+            if self.measure_clip_length > 1 and self.state == 'measure':
+                if not self._run_clip(frame):
+                    break
+            else:
+                self.step(frame)
             self.update_ui()
             self.sync_to_fps()
         logging.info("Capture closed.")
         self.cap.release()
+
+    def _add_benchmark_tags(self):
+        for tag in ('Measurement Loop', 'Frame Capture', 'Calibration Measurement'):
+            if not self.benchmarker.has_tag(tag):
+                self.benchmarker.add_tag(tag)
+
+    # Frames of the 'measure' state that run() collects into one device buffer and hands to step_clip() in one go.  1: run() steps
+    # frame by frame, as the reference does.
+    measure_clip_length = 1
+
+    def _run_clip(self, frame):
+        """`frame` and up to measure_clip_length - 1 further captured frames as one clip; False when the capture ended."""
+        K = int(self.measure_clip_length)
+        buf = getattr(self, "_clip_buf", None)
+        if buf is None or len(buf) != K or tuple(buf.shape[1:]) != tuple(frame.shape):
+            if isinstance(frame, np.ndarray):
+                buf = np.empty((K,) + tuple(frame.shape), dtype=np.uint8)
+            else:
+                t = device.torch()
+                buf = t.empty((K,) + tuple(frame.shape), dtype=t.uint8, device=frame.device)
+            self._clip_buf = buf
+        buf[0] = frame
+        n, open_ = 1, True
+        while n < K:
+            self.benchmarker.tick_start('Frame Capture')
+            frame = self.next_frame()
+            if isinstance(frame, bool):
+                open_ = False
+                break
+            self.benchmarker.tick_end('Frame Capture')
+            buf[n] = frame
+            n += 1
+        done = 0
+        while done < n:
+            done += self.step_clip(buf[done:n])
+        return open_
+
+    def step_clip(self, frames):
+        """`for f in frames: step(f)` (each f being the current frame, as after next_frame()) with the device work of the 'measure'
+        state done per clip: one rm_roi_mean_clip call, or one rm_flow_clip plus one rm_pca_reduce_windows call, then the per-frame
+        host bookkeeping replayed in order.  frames: [N,H,W] gray frames, a device tensor or a numpy array.  Returns the number of
+        frames consumed: it stops behind the frame on which the state leaves 'measure'; frames met in any other state go through
+        step() one by one."""
+        self._add_benchmark_tags()
+        if isinstance(frames, np.ndarray) and isinstance(self._backend, _Backend):
+            frames = device.to_device(frames)
+        n, done = len(frames), 0
+        while done < n:
+            if self.state != 'measure':
+                self._step_frame(frames[done])
+                done += 1
+                continue
+            done += self._measure_clip(frames[done:])
+            if self.state != 'measure':
+                break
+        return done
+
+    def _step_frame(self, frame):
+        self._frame_u8, self._frame_bgr = frame, None
+        self.step(frame)
+
+    def _measure_clip(self, frames):
+        x, y, w, h = self.x, self.y, self.w, self.h
+        be = self._backend
+        n = len(frames)
+        if self.motion_extraction_method == "average":
+            means = be.roi_mean_clip(frames, x, y, w, h)
+            value_of = lambda i: float(means[i])
+        else:
+            begun = self.previous_cropped_image
+            if (not self.fused_flow_step or not hasattr(be, "flow_clip") or (begun is not None and begun is not self._RESIDENT)
+                    or len(self.motion_data) > self.measure_buffer_length):
+                for i in range(n):                                           # the per-frame calls (four-call path, or a backend without clips)
+                    self._step_frame(frames[i])
+                    if self.state != 'measure':
+                        return i + 1
+                return n
+            if begun is None:                                               # base.py:363-369: the corners come from the first frame
+                self._step_frame(frames[0])
+                if n == 1 or self.state != 'measure':
+                    return 1
+                return 1 + self._measure_clip(frames[1:])
+            value_of = self._flow_clip_values(be, frames, x, y, w, h)
+        for i in range(n):
+            self.benchmarker.tick_start('Measurement Loop')
+            self._frame_u8, self._frame_bgr = frames[i], None
+            self.cropped_image = (x, y, w, h)
+            self._pop_full_buffers()
+            self._record_value(value_of(i))
+            self.benchmarker.tick_end('Measurement Loop')
+            if self.state != 'measure':
+                return i + 1
+        return n
+
+    def _flow_clip_values(self, be, frames, x, y, w, h):
+        """The device work of a clip in 'flow' mode; returns value(i) = what extract_motion() returns for frame i, to be called once
+        per frame, in order, behind the popleft rule of base.py:473-475 (it does extract_motion's bookkeeping on motion_data).
+        The clip is tracked to its end even if the replay then stops at an error frame.  That is harmless: both error causes ("No
+        motion key points found.", a NaN value) leave the state without points, so the frames behind the error only advanced its
+        previous image, and reset() discards the flow state before tracking begins again."""
+        had_points = self._flow_n > 0
+        mean, n_good = be.flow_clip(self._flow_state, frames, x, y, w, h, **self.lk_params)
+        if not had_points:
+            return lambda i: np.nan
+        self._points_stale = True
+        # rows this clip appends to motion_data: the frames in front of the one that loses the last point.  The deque holds at most
+        # measure_buffer_length rows (popleft before every frame), so frame i's PCA runs over that many rows ending in its own.
+        k = 0
+        while k < len(n_good) and n_good[k] > 0:
+            k += 1
+        first = len(self.motion_data)
+        pca = []
+        if k:
+            rows = np.array(list(self.motion_data) + [[mean[i][0], mean[i][1]] for i in range(k)], dtype=np.float32)
+            pca = be.pca_reduce_windows(rows, first, self.measure_buffer_length)
+
+        def value(i):
+            if self._flow_n == 0:
+                return np.nan
+            self._flow_n = int(n_good[i])
+            if self._flow_n == 0:
+                return np.nan                                               # base.py:385-386 (the object np.nan: detect_errors tests identity)
+            self.motion_data.append([mean[i][0], mean[i][1]])               # base.py:389
+            if len(self.motion_data) >= 2:
+                return float(pca[i])                                        # base.py:396-405
+            return 0.0
+        return value
 
     def step(self, frame):
         """One iteration of the reference's state dispatch (base.py:423-500) on an already captured frame."""
@@ -654,27 +818,33 @@ class RespiratoryMonitor:
         elif self.state == 'measure':
             self.benchmarker.tick_start('Measurement Loop')
             self.cropped_image = (self.x, self.y, self.w, self.h)           # base.py:471 (a view descriptor)
-            for b in self.buffers:                                          # base.py:473-475
-                if len(b) >= self.measure_buffer_length:
-                    b.popleft()
-            value = self.extract_motion()
-            self.data.append(value)
-            if len(self.t) == 0:
-                self.t.append(0.)
-            else:
-                self.t.append(self.t[-1] + (1. / self.fps))
-            if self.save_all_data:
-                self.all_data.append((self.t[-1], value))
-            if len(self.data) > self.measure_initialization_length:
-                self.measure()
-                if not self.disable_error_detection and self.detect_errors():
-                    self.trigger_error("error detection found poor signal")
+            self._pop_full_buffers()
+            self._record_value(self.extract_motion())
             self.benchmarker.tick_end('Measurement Loop')
         elif self.state == 'error':
             if time.time() - self.reset_start_time >= self.error_reset_delay:
                 logging.info('Benchmark Report...\r\n' + self.benchmarker.get_report())
                 self.reset()
                 self.state = 'calibration'
+
+    def _pop_full_buffers(self):
+        for b in self.buffers:                                              # base.py:473-475
+            if len(b) >= self.measure_buffer_length:
+                b.popleft()
+
+    def _record_value(self, value):
+        """What the 'measure' state does with the value of one frame (base.py:477-497)."""
+        self.data.append(value)
+        if len(self.t) == 0:
+            self.t.append(0.)
+        else:
+            self.t.append(self.t[-1] + (1. / self.fps))
+        if self.save_all_data:
+            self.all_data.append((self.t[-1], value))
+        if len(self.data) > self.measure_initialization_length:
+            self.measure()
+            if not self.disable_error_detection and self.detect_errors():
+                self.trigger_error("error detection found poor signal")
 
     def _locate_buffer(self):
         """the locate() call of run(), base.py:444-448: threshold = int(round(0.08*255)) = 20; pyramid_levels=9,

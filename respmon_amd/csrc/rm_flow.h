@@ -218,9 +218,9 @@ inline int flow_good_features(FlowWorkspace &ws, const uint8_t *img, int h, int 
 // calcOpticalFlowPyrLK  
 // ----------------------------------------------------------------------------------------
 // uint8 pyrDown: integer 5-tap, (sum + 128) >> 8, BORDER_REFLECT_101
-RM_KERNEL __launch_bounds__(256) void k_pyr_down_u8(const uint8_t *src, int h, int w, uint8_t *dst, int dh, int dw)
+// (output pixel i of one image; shared by the per-image kernel and the per-clip kernel of rm_flow_clip.h)
+__device__ __forceinline__ void pyr_down_u8_px(const uint8_t *src, int h, int w, uint8_t *dst, int dh, int dw, int i)
 {
-    int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= dh * dw) return;
     int y = i / dw, x = i - y * dw;
     int rows[5];
@@ -233,11 +233,14 @@ RM_KERNEL __launch_bounds__(256) void k_pyr_down_u8(const uint8_t *src, int h, i
     int v = rows[2] * 6 + (rows[1] + rows[3]) * 4 + rows[0] + rows[4];
     dst[i] = (uint8_t)((v + 128) >> 8);
 }
+RM_KERNEL __launch_bounds__(256) void k_pyr_down_u8(const uint8_t *src, int h, int w, uint8_t *dst, int dh, int dw)
+{
+    pyr_down_u8_px(src, h, w, dst, dh, dw, blockIdx.x * 256 + threadIdx.x);
+}
 
 // calcSharrDeriv: int16 (Ix, Iy) interleaved; reflect-101 inside the image
-RM_KERNEL __launch_bounds__(256) void k_scharr(const uint8_t *src, int h, int w, short *d)
+__device__ __forceinline__ void scharr_px(const uint8_t *src, int h, int w, short *d, int i)
 {
-    int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= h * w) return;
     int y = i / w, x = i - y * w;
     const uint8_t *r0 = src + (size_t)(y > 0 ? y - 1 : (h > 1 ? 1 : 0)) * w;
@@ -249,6 +252,10 @@ RM_KERNEL __launch_bounds__(256) void k_scharr(const uint8_t *src, int h, int w,
     d[2 * (size_t)i] = (short)(t0(xp) - t0(xm));
     d[2 * (size_t)i + 1] = (short)((t1(xp) + t1(xm)) * 3 + t1(x) * 10);
 }
+RM_KERNEL __launch_bounds__(256) void k_scharr(const uint8_t *src, int h, int w, short *d)
+{
+    scharr_px(src, h, w, d, blockIdx.x * 256 + threadIdx.x);
+}
 
 constexpr int LK_MAX_LEVELS = 8;
 constexpr int LK_MAX_WIN = 1024;  // taps per window (winSize up to 32x32)
@@ -258,6 +265,9 @@ struct LKLevels {
     int h[LK_MAX_LEVELS], w[LK_MAX_LEVELS];
     const uint8_t *prev[LK_MAX_LEVELS], *next[LK_MAX_LEVELS];
     const short *deriv[LK_MAX_LEVELS];
+    // a clip's images lie stride[l] pixels apart (rm_flow_clip.h): frame f tracks from prev[l] + f * stride[l] to next[l] + f * stride[l]
+    // with the derivatives at deriv[l] + 2 * f * stride[l].  Unused (frame 0) by the one-pair entry points.
+    size_t stride[LK_MAX_LEVELS];
 };
 
 __device__ __forceinline__ int lk_px(const uint8_t *img, int h, int w, int y, int x)
@@ -300,30 +310,30 @@ __device__ __forceinline__ void lk_seq_sum3(const float *a, const float *b, cons
 // accumulations run as one raster-order chain (replicated in every lane) to match OpenCV's generic path.
 // ROUNDS: trips of the tap loops (lane k, k + 64, ...), unrolled so that the gathers of all of a window's taps are in flight
 // together: 4 covers winSize up to 16 x 16 (the reference's 15 x 15, base.py:96), 16 the 32 x 32 maximum.
+// lk_track_point: one point through one pair of images (the whole workgroup = one wave calls it together; the LDS arrays are the
+// caller's).  `frame` selects the pair inside a clip (LKLevels::stride); the one-pair kernel passes 0.  out_x / out_y / st: what
+// OpenCV leaves in nextPts / status.
 template <int ROUNDS>
-__global__ __launch_bounds__(64) void k_lk_track(LKLevels L, const float *pts_in, int npts, int win_w, int win_h, int max_count,
-                                                 double epsilon, float *pts_out, uint8_t *status)
+__device__ __forceinline__ void lk_track_point(const LKLevels &L, size_t frame, float px_in, float py_in, int win_w, int win_h, int max_count,
+                                               double epsilon, short *s_I, short *s_dI, float *s_t0, float *s_t1, float *s_t2, float &out_x,
+                                               float &out_y, int &st)
 {
-    __shared__ short s_I[LK_MAX_WIN];
-    __shared__ short s_dI[2 * LK_MAX_WIN];
-    __shared__ __attribute__((aligned(16))) float s_t0[LK_MAX_WIN], s_t1[LK_MAX_WIN], s_t2[LK_MAX_WIN];
-    const int p = blockIdx.x, lane = threadIdx.x;
-    if (p >= npts) return;
+    const int lane = threadIdx.x;
     const int ntap = win_w * win_h;
     const float half_x = (win_w - 1) * 0.5f, half_y = (win_h - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (1 << 20);
     const int W_BITS = 14;
     const float min_eig_threshold = (float)1e-4;
-    const float px_in = pts_in[2 * p], py_in = pts_in[2 * p + 1];
     int tap_y[ROUNDS], tap_x[ROUNDS];     // window position of this lane's taps (one integer division each, once)
 #pragma unroll
     for (int rnd = 0; rnd < ROUNDS; ++rnd) { const int k = lane + 64 * rnd; tap_y[rnd] = k / win_w; tap_x[rnd] = k - tap_y[rnd] * win_w; }
-    float out_x = 0.f, out_y = 0.f;
-    int st = 1;
+    out_x = 0.f; out_y = 0.f;
+    st = 1;
     for (int level = L.n - 1; level >= 0; --level) {
         const int h = L.h[level], w = L.w[level];
-        const uint8_t *I = L.prev[level], *J = L.next[level];
-        const short *dI = L.deriv[level];
+        const size_t off = frame * L.stride[level];
+        const uint8_t *I = L.prev[level] + off, *J = L.next[level] + off;
+        const short *dI = L.deriv[level] + 2 * off;
         const float sc = (float)(1. / (1 << level));
         float prev_x = px_in * sc, prev_y = py_in * sc;
         float next_x, next_y;
@@ -406,6 +416,20 @@ __global__ __launch_bounds__(64) void k_lk_track(LKLevels L, const float *pts_in
             pdx = dx; pdy = dy;
         }
     }
+}
+
+template <int ROUNDS>
+__global__ __launch_bounds__(64) void k_lk_track(LKLevels L, const float *pts_in, int npts, int win_w, int win_h, int max_count,
+                                                 double epsilon, float *pts_out, uint8_t *status)
+{
+    __shared__ short s_I[LK_MAX_WIN];
+    __shared__ short s_dI[2 * LK_MAX_WIN];
+    __shared__ __attribute__((aligned(16))) float s_t0[LK_MAX_WIN], s_t1[LK_MAX_WIN], s_t2[LK_MAX_WIN];
+    const int p = blockIdx.x, lane = threadIdx.x;
+    if (p >= npts) return;
+    float out_x, out_y;
+    int st;
+    lk_track_point<ROUNDS>(L, 0, pts_in[2 * p], pts_in[2 * p + 1], win_w, win_h, max_count, epsilon, s_I, s_dI, s_t0, s_t1, s_t2, out_x, out_y, st);
     if (lane == 0) { pts_out[2 * p] = out_x; pts_out[2 * p + 1] = out_y; status[p] = (uint8_t)st; }
 }
 
@@ -434,7 +458,7 @@ inline int flow_pyr_lk_dev(FlowWorkspace &ws, const uint8_t *prev, const uint8_t
     epsilon *= epsilon;
     max_level = lk_max_level(h, w, win_w, win_h, max_level);
     if (max_level + 1 > LK_MAX_LEVELS) { err = "too many pyramid levels"; return RM_E_UNSUPPORTED; }
-    LKLevels L;
+    LKLevels L = {};
     L.n = max_level + 1;
     int sh = h, sw = w;
     for (int l = 0; l <= max_level; ++l) {
@@ -487,9 +511,9 @@ inline int flow_pyr_lk(FlowWorkspace &ws, const uint8_t *prev, const uint8_t *ne
 // lane 0 adds the differences in point order from LDS.  (One THREAD walking global memory took 150 us for 1 000 points.)
 constexpr int FLOW_FINISH_MAX = 6000;   // points whose differences fit the LDS staging (2 floats each)
 __host__ __device__ __forceinline__ int flow_finish_pitch(int n) { return (n + 3) & ~3; }   // floats per staged component
-RM_KERNEL __launch_bounds__(64) void k_flow_finish(const float *o, const float *nw, const uint8_t *st, int n, float *res, float *next_pts)
+// (the wave's work; next_pts may be null: the frames of a clip that nothing tracks from, rm_flow_clip.h)
+__device__ __forceinline__ void flow_finish_wave(const float *o, const float *nw, const uint8_t *st, int n, float *res, float *next_pts, float *s_d)
 {
-    HIP_DYNAMIC_SHARED(float, s_d)     // [2 * flow_finish_pitch(n)]: dx of the survivors, then dy (both 16-byte aligned: lk_seq_sum2 reads float4)
     const int lane = threadIdx.x;
     float *s_dx = s_d, *s_dy = s_d + flow_finish_pitch(n);
     int base = 0;
@@ -501,7 +525,7 @@ RM_KERNEL __launch_bounds__(64) void k_flow_finish(const float *o, const float *
         const unsigned long long m = __ballot(good);
         if (good) {
             const int slot = base + (int)__popcll(m & ((1ull << lane) - 1ull));
-            next_pts[2 * slot] = nx; next_pts[2 * slot + 1] = ny;
+            if (next_pts) { next_pts[2 * slot] = nx; next_pts[2 * slot + 1] = ny; }
             s_dx[slot] = ox - nx; s_dy[slot] = oy - ny;
         }
         base += (int)__popcll(m);
@@ -515,20 +539,29 @@ RM_KERNEL __launch_bounds__(64) void k_flow_finish(const float *o, const float *
         res[2] = (float)base;
     }
 }
+RM_KERNEL __launch_bounds__(64) void k_flow_finish(const float *o, const float *nw, const uint8_t *st, int n, float *res, float *next_pts)
+{
+    HIP_DYNAMIC_SHARED(float, s_d)     // [2 * flow_finish_pitch(n)]: dx of the survivors, then dy (both 16-byte aligned: lk_seq_sum2 reads float4)
+    flow_finish_wave(o, nw, st, n, res, next_pts, s_d);
+}
 // (more points than the staging holds: one thread, global memory)
-RM_KERNEL void k_flow_finish_seq(const float *o, const float *nw, const uint8_t *st, int n, float *res, float *next_pts)
+__device__ __forceinline__ void flow_finish_seq(const float *o, const float *nw, const uint8_t *st, int n, float *res, float *next_pts)
 {
     float sx = 0.f, sy = 0.f;
     int m = 0;
     for (int i = 0; i < n; ++i)
         if (st[i] == 1) {
             sx += o[2 * i] - nw[2 * i]; sy += o[2 * i + 1] - nw[2 * i + 1];
-            next_pts[2 * m] = nw[2 * i]; next_pts[2 * m + 1] = nw[2 * i + 1];
+            if (next_pts) { next_pts[2 * m] = nw[2 * i]; next_pts[2 * m + 1] = nw[2 * i + 1]; }
             ++m;
         }
     res[0] = m ? sx / (float)m : 0.f;
     res[1] = m ? sy / (float)m : 0.f;
     res[2] = (float)m;
+}
+RM_KERNEL void k_flow_finish_seq(const float *o, const float *nw, const uint8_t *st, int n, float *res, float *next_pts)
+{
+    flow_finish_seq(o, nw, st, n, res, next_pts);
 }
 
 // Device-resident state of one extract_motion('flow') session (rm_flow_state): the two ROI crops a step works on -- the
@@ -565,7 +598,7 @@ inline int flow_track_resident(FlowState &fs, int prev_side, int cur_side, const
     epsilon *= epsilon;
     max_level = lk_max_level(h, w, win_w, win_h, max_level);
     if (max_level + 1 > LK_MAX_LEVELS) { err = "too many pyramid levels"; return RM_E_UNSUPPORTED; }
-    LKLevels L;
+    LKLevels L = {};
     L.n = max_level + 1;
     int sh = h, sw = w;
     for (int l = 0; l <= max_level; ++l) {
@@ -710,7 +743,7 @@ __device__ inline void eig2x2_dgeev(double a, double b, double c, double d, doub
     v[0][0] = v1[0] * n1; v[1][0] = v1[1] * n1; v[0][1] = v2[0] * n2; v[1][1] = v2[1] * n2;
 }
 
-RM_KERNEL __launch_bounds__(64) void k_pca_reduce(const float *motion, int n, double *out)
+__device__ __forceinline__ void pca_reduce_wave(const float *motion, int n, double *out)
 {
     const int lane = threadIdx.x;
     double sx = 0, sy = 0;
@@ -733,6 +766,10 @@ RM_KERNEL __launch_bounds__(64) void k_pca_reduce(const float *motion, int n, do
         const double e0 = v[0][i0], e1 = v[0][i1];
         out[0] = (double)motion[2 * (n - 1)] * e0 + (double)motion[2 * (n - 1) + 1] * e1;
     }
+}
+RM_KERNEL __launch_bounds__(64) void k_pca_reduce(const float *motion, int n, double *out)
+{
+    pca_reduce_wave(motion, n, out);
 }
 
 inline int flow_pca(FlowWorkspace &ws, const float *motion, int n, double *out, hipStream_t s, std::string &err)

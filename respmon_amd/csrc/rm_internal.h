@@ -44,6 +44,7 @@
 #include "rm_xstore.h"
 #include "rm_ccl.h"
 #include "rm_flow.h"
+#include "rm_flow_clip.h"
 
 // sets the thread's error string (rm_last_error_string) and returns `code`
 int fail(int code, const char *fmt, ...);
@@ -132,6 +133,7 @@ struct DebugKnobs {
     int tile_sum_half = -1;       // 0 / 1: k_tile_sum works on whole tiles / half tiles whatever the number of heavy tiles (-1: by that number)
     long long store_default_slots = 0;   // > 0: slots the value store starts with before any selection has made it grow (default 16 384)
     long long store_slots = 0;    // > 0: capacity of the value store in (tile, frame) slots (forces the overflow path)
+    long long flow_clip_bytes = 0;   // > 0: workspace cap of one chunk of rm_flow_clip (default 256 MiB): a chunk holds max(1, cap / slot - 1) frames, slot = 5 bytes per pixel of every LK pyramid level of the ROI
 };
 
 // pinned result areas of ONE ROI extraction in flight

@@ -2633,9 +2633,8 @@ RM_KERNEL __launch_bounds__(256) void k_f64_to_u8(const double *src, uint8_t *ds
 // np.average(frame[y:y+h, x:x+w]) (base.py:357): numpy's pairwise order is not reproduced; any
 // float64 order is within ~1e-13 relative of it.  One block; wave partials summed in lane order.
 template <typename Tin>
-__global__ __launch_bounds__(256) void k_roi_mean(const Tin *frame, int W, int x, int y, int w, int h, double *out)
+__device__ __forceinline__ void roi_mean_block(const Tin *frame, int W, int x, int y, int w, int h, double *out, double *s_part)
 {
-    __shared__ double s_part[4];
     double acc = 0.0;
     int n = w * h;
     for (int i = threadIdx.x; i < n; i += 256) {
@@ -2649,13 +2648,42 @@ __global__ __launch_bounds__(256) void k_roi_mean(const Tin *frame, int W, int x
 }
 
 template <typename Tin>
-__global__ __launch_bounds__(256) void k_roi_to_u8(const Tin *frame, int W, int x, int y, int w, int h, uint8_t *dst)
+__global__ __launch_bounds__(256) void k_roi_mean(const Tin *frame, int W, int x, int y, int w, int h, double *out)
+{
+    __shared__ double s_part[4];
+    roi_mean_block(frame, W, x, y, w, h, out, s_part);
+}
+
+// the same reduction for every frame of a resident [N,H,W] clip: workgroup i sums frame i in k_roi_mean's order (rm_roi_mean_clip)
+template <typename Tin>
+__global__ __launch_bounds__(256) void k_roi_mean_clip(const Tin *frames, size_t frame_px, int W, int x, int y, int w, int h, double *out)
+{
+    __shared__ double s_part[4];
+    roi_mean_block(frames + (size_t)blockIdx.x * frame_px, W, x, y, w, h, out + blockIdx.x, s_part);
+}
+
+template <typename Tin>
+__device__ __forceinline__ void roi_to_u8_grid(const Tin *frame, int W, int x, int y, int w, int h, uint8_t *dst)
 {
     int n = w * h;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         int r = i / w, c = i - r * w;
         dst[i] = f64_to_u8_trunc(load_px(frame, (size_t)(y + r) * W + x + c) * 255);
     }
+}
+
+template <typename Tin>
+__global__ __launch_bounds__(256) void k_roi_to_u8(const Tin *frame, int W, int x, int y, int w, int h, uint8_t *dst)
+{
+    roi_to_u8_grid(frame, W, x, y, w, h, dst);
+}
+
+// ... and the crops of a clip's frames in one launch: blockIdx.y is the frame, the crops lie `dst_stride` bytes apart (rm_flow_clip)
+template <typename Tin>
+__global__ __launch_bounds__(256) void k_roi_to_u8_clip(const Tin *frames, size_t frame_px, int W, int x, int y, int w, int h, uint8_t *dst,
+                                                        size_t dst_stride)
+{
+    roi_to_u8_grid(frames + (size_t)blockIdx.y * frame_px, W, x, y, w, h, dst + (size_t)blockIdx.y * dst_stride);
 }
 
 // cv2.cvtColor(BGR2GRAY), base.py:230: Y = (B*1868 + G*9617 + R*4899 + 8192) >> 14

@@ -229,6 +229,178 @@ extern "C" int rm_flow_points(rm_ctx *ctx, rm_flow_state *state, float *pts_host
 }
 
 // ------------------------------------------------------------------------------------------
+// a whole resident clip per call: one host synchronisation, launches that do not grow with the number of frames
+// ------------------------------------------------------------------------------------------
+extern "C" int rm_roi_mean_clip(rm_ctx *ctx, const void *frames, int dtype, int N, int H, int W, int x, int y, int w, int h, double *out,
+                                void *stream)
+{
+    if (!ctx || !frames || !out || N < 1 || !valid_dtype(dtype) || !roi_ok(H, W, x, y, w, h)) return fail(RM_E_BADARG, "rm_roi_mean_clip: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    double *d = nullptr;
+    RM_TRY(ws(ctx, "roi_mean_clip", (size_t)N, &d));
+    const size_t px = (size_t)H * W;
+    switch (dtype) {
+    case RM_U8: hipLaunchKernelGGL((k_roi_mean_clip<uint8_t>), dim3(N), dim3(256), 0, s, (const uint8_t *)frames, px, W, x, y, w, h, d); break;
+    case RM_F16: hipLaunchKernelGGL((k_roi_mean_clip<__half>), dim3(N), dim3(256), 0, s, (const __half *)frames, px, W, x, y, w, h, d); break;
+    case RM_F32: hipLaunchKernelGGL((k_roi_mean_clip<float>), dim3(N), dim3(256), 0, s, (const float *)frames, px, W, x, y, w, h, d); break;
+    default: hipLaunchKernelGGL((k_roi_mean_clip<double>), dim3(N), dim3(256), 0, s, (const double *)frames, px, W, x, y, w, h, d); break;
+    }
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(out, d, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    return RM_OK;
+}
+
+extern "C" int rm_pca_reduce_windows(rm_ctx *ctx, const float *motion, int n, int first, int window, double *out, void *stream)
+{
+    if (!ctx || !motion || !out || n < 0 || first < 0 || first > n || window < 1) return fail(RM_E_BADARG, "rm_pca_reduce_windows: bad argument");
+    if (first == n) return RM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    std::string err;
+    float *d_m = nullptr;
+    double *d_o = nullptr;
+    int rc;
+    if ((rc = ctx->flow.get("pcaw_in", sizeof(float) * 2 * (size_t)n, (void **)&d_m, err)) < 0) return fail(rc, "%s", err.c_str());
+    if ((rc = ctx->flow.get("pcaw_out", sizeof(double) * (size_t)(n - first), (void **)&d_o, err)) < 0) return fail(rc, "%s", err.c_str());
+    HIP_TRY(hipMemcpyAsync(d_m, motion, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_pca_reduce_windows<>, dim3(n - first), dim3(64), 0, s, d_m, first, window, d_o);
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(out, d_o, sizeof(double) * (size_t)(n - first), hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    return RM_OK;
+}
+
+// the crops of `n` frames of a clip, `dst_stride` bytes apart, in one launch
+static int flow_crop_clip(const void *frames, int dtype, int n, int H, int W, int x, int y, int w, int h, uint8_t *dst, size_t dst_stride, hipStream_t s)
+{
+    const size_t px = (size_t)H * W;
+    dim3 grid(nblk((size_t)w * h, 256, 1024), n), block(256);
+    switch (dtype) {
+    case RM_U8: hipLaunchKernelGGL((k_roi_to_u8_clip<uint8_t>), grid, block, 0, s, (const uint8_t *)frames, px, W, x, y, w, h, dst, dst_stride); break;
+    case RM_F16: hipLaunchKernelGGL((k_roi_to_u8_clip<__half>), grid, block, 0, s, (const __half *)frames, px, W, x, y, w, h, dst, dst_stride); break;
+    case RM_F32: hipLaunchKernelGGL((k_roi_to_u8_clip<float>), grid, block, 0, s, (const float *)frames, px, W, x, y, w, h, dst, dst_stride); break;
+    default: hipLaunchKernelGGL((k_roi_to_u8_clip<double>), grid, block, 0, s, (const double *)frames, px, W, x, y, w, h, dst, dst_stride); break;
+    }
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
+constexpr long long FLOW_CLIP_BYTES = 256ll << 20;   // workspace cap of one chunk's crops, pyramids and derivatives (rm_debug_set flow_clip_bytes)
+constexpr int FLOW_CLIP_MAX_CHUNK = 32768;           // frames per chunk at most: the image index is a grid's y dimension
+
+// N successive rm_flow_step calls as one: see rm_flow_clip.h for the shape of the device work.  The clip is worked through in chunks
+// of C frames whose images (the chunk's frames behind image 0, the crop the chunk tracks from) share one workspace; a point keeps its
+// index through all chunks, its position and life going from one chunk's tracker to the next through `carry`.
+extern "C" int rm_flow_clip(rm_ctx *ctx, rm_flow_state *state, const void *frames, int dtype, int N, int H, int W, int x, int y, int w, int h,
+                            int win_w, int win_h, int max_level, int max_count, double epsilon, float *mean_xy_host, int *n_good_host, void *stream)
+{
+    if (!ctx || !state || !frames || !mean_xy_host || !n_good_host || N < 1 || !valid_dtype(dtype) || !roi_ok(H, W, x, y, w, h) || win_w < 3 ||
+        win_h < 3 || max_level < 0)
+        return fail(RM_E_BADARG, "rm_flow_clip: bad argument");
+    FlowState &fs = state->fs;
+    if (!fs.begun || w != fs.w || h != fs.h) return fail(RM_E_BADARG, "rm_flow_clip: rm_flow_begin has not been called on this state for this ROI size");
+    if (state->device != ctx->device) return fail(RM_E_BADARG, "rm_flow_clip: the flow state belongs to another device");
+    const int npts = fs.npts;
+    if (npts > 0) {   // (rm_flow_step meets these limits in its tracking stage, which a state without points never reaches)
+        if (win_w * win_h > LK_MAX_WIN) return fail(RM_E_UNSUPPORTED, "winSize too large");
+        if (lk_max_level(h, w, win_w, win_h, max_level) + 1 > LK_MAX_LEVELS) return fail(RM_E_UNSUPPORTED, "too many pyramid levels");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t frame_bytes = (size_t)H * W * dtype_size(dtype);
+    const int prev_side = fs.flip, cur_side = fs.flip ^ 1;
+    uint8_t *prev = nullptr, *cur = nullptr; float *pa = nullptr, *pb = nullptr;
+    RM_TRY(flow_state_crop(fs, prev_side, &prev));
+    RM_TRY(flow_state_crop(fs, cur_side, &cur));
+    RM_TRY(flow_state_pts(fs, &pa, &pb));
+    for (int i = 0; i < N; ++i) { mean_xy_host[2 * i] = mean_xy_host[2 * i + 1] = 0.f; n_good_host[i] = 0; }
+    if (npts == 0) {   // nothing to track: the previous image advances to the clip's last frame (base.py:381)
+        RM_TRY(flow_crop(ctx, (const char *)frames + (size_t)(N - 1) * frame_bytes, dtype, H, W, x, y, w, h, cur, s));
+        fs.pyr_levels[cur_side] = 0; fs.deriv_levels[cur_side] = -1;
+        fs.flip ^= 1;
+        return RM_OK;
+    }
+    if (max_count < 0) max_count = 0;
+    if (max_count > 100) max_count = 100;
+    if (epsilon < 0) epsilon = 0;
+    if (epsilon > 10) epsilon = 10;
+    epsilon *= epsilon;
+    max_level = lk_max_level(h, w, win_w, win_h, max_level);
+    LKLevels L = {};
+    L.n = max_level + 1;
+    size_t slot_bytes = 0;
+    for (int l = 0, sh = h, sw = w; l <= max_level; ++l, sh = (sh + 1) / 2, sw = (sw + 1) / 2) {
+        L.h[l] = sh; L.w[l] = sw; L.stride[l] = (size_t)sh * sw;
+        slot_bytes += L.stride[l] * (1 + 2 * sizeof(short));
+    }
+    const long long cap = ctx->dbg.flow_clip_bytes > 0 ? ctx->dbg.flow_clip_bytes : FLOW_CLIP_BYTES;
+    const int C = (int)std::max<long long>(1, std::min<long long>(std::min(N, FLOW_CLIP_MAX_CHUNK), cap / (long long)slot_bytes - 1));
+    std::string err;
+    int rc;
+    uint8_t *img[LK_MAX_LEVELS]; short *der[LK_MAX_LEVELS];
+    for (int l = 0; l <= max_level; ++l) {
+        if ((rc = fs.ws.get("clip_img" + std::to_string(l), L.stride[l] * (size_t)(C + 1), (void **)&img[l], err)) < 0) return fail(rc, "%s", err.c_str());
+        if ((rc = fs.ws.get("clip_deriv" + std::to_string(l), L.stride[l] * 2 * sizeof(short) * (size_t)C, (void **)&der[l], err)) < 0) return fail(rc, "%s", err.c_str());
+        L.prev[l] = img[l]; L.next[l] = img[l] + L.stride[l]; L.deriv[l] = der[l];
+    }
+    float *d_pos = nullptr, *d_res = nullptr, *carry_p[2] = {nullptr, nullptr}; uint8_t *d_st = nullptr, *carry_a[2] = {nullptr, nullptr};
+    if ((rc = fs.ws.get("clip_pos", sizeof(float) * 2 * (size_t)npts * C, (void **)&d_pos, err)) < 0) return fail(rc, "%s", err.c_str());
+    if ((rc = fs.ws.get("clip_status", (size_t)npts * C, (void **)&d_st, err)) < 0) return fail(rc, "%s", err.c_str());
+    if ((rc = fs.ws.get("clip_res", sizeof(float) * 4 * (size_t)N, (void **)&d_res, err)) < 0) return fail(rc, "%s", err.c_str());
+    for (int k = 0; k < 2; ++k) {
+        if ((rc = fs.ws.get(k ? "clip_carry_pts_b" : "clip_carry_pts_a", sizeof(float) * 2 * (size_t)npts, (void **)&carry_p[k], err)) < 0) return fail(rc, "%s", err.c_str());
+        if ((rc = fs.ws.get(k ? "clip_carry_alive_b" : "clip_carry_alive_a", (size_t)npts, (void **)&carry_a[k], err)) < 0) return fail(rc, "%s", err.c_str());
+    }
+    float *pts = fs.flip ? pb : pa, *pts_next = fs.flip ? pa : pb;
+    HIP_TRY(hipMemcpyAsync(carry_p[0], pts, sizeof(float) * 2 * (size_t)npts, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(carry_a[0], 1, (size_t)npts, s));
+    HIP_TRY(hipMemcpyAsync(img[0], prev, L.stride[0], hipMemcpyDeviceToDevice, s));
+    int last = 0;   // the image of the chunk just done that holds its last frame
+    for (int c0 = 0, k = 0; c0 < N; c0 += C, ++k) {
+        const int n = std::min(C, N - c0);
+        const bool final_chunk = c0 + n == N;
+        // frame-parallel front: crops into images 1 .. n, the pyramids of images 0 .. n, the derivatives of images 0 .. n - 1
+        RM_TRY(flow_crop_clip((const char *)frames + (size_t)c0 * frame_bytes, dtype, n, H, W, x, y, w, h, img[0] + L.stride[0], L.stride[0], s));
+        for (int l = 1; l <= max_level; ++l)
+            hipLaunchKernelGGL(k_pyr_down_u8_clip<>, dim3((unsigned)((L.stride[l] + 255) / 256), n + 1), dim3(256), 0, s, img[l - 1], L.stride[l - 1],
+                               L.h[l - 1], L.w[l - 1], img[l], L.stride[l], L.h[l], L.w[l]);
+        for (int l = 0; l <= max_level; ++l)
+            hipLaunchKernelGGL(k_scharr_clip<>, dim3((unsigned)((L.stride[l] + 255) / 256), n), dim3(256), 0, s, img[l], L.stride[l], L.h[l], L.w[l], der[l]);
+        // point-parallel tracker, frame-parallel finish
+        const float *start = carry_p[k & 1]; const uint8_t *start_alive = carry_a[k & 1];
+        if (win_w * win_h <= 256)
+            hipLaunchKernelGGL(k_lk_track_clip<4>, dim3(npts), dim3(64), 0, s, L, n, start, start_alive, npts, win_w, win_h, max_count, epsilon, d_pos, d_st,
+                               carry_p[(k + 1) & 1], carry_a[(k + 1) & 1]);
+        else
+            hipLaunchKernelGGL(k_lk_track_clip<16>, dim3(npts), dim3(64), 0, s, L, n, start, start_alive, npts, win_w, win_h, max_count, epsilon, d_pos, d_st,
+                               carry_p[(k + 1) & 1], carry_a[(k + 1) & 1]);
+        float *next_pts = final_chunk ? pts_next : nullptr;
+        if (npts <= FLOW_FINISH_MAX)
+            hipLaunchKernelGGL(k_flow_finish_clip<>, dim3(n), dim3(64), 2 * sizeof(float) * (size_t)flow_finish_pitch(npts), s, start, d_pos, d_st, npts, n,
+                               d_res + 4 * (size_t)c0, next_pts);
+        else
+            hipLaunchKernelGGL(k_flow_finish_clip_seq<>, dim3(n), dim3(1), 0, s, start, d_pos, d_st, npts, n, d_res + 4 * (size_t)c0, next_pts);
+        LAUNCH_CHECK();
+        last = n;
+        if (!final_chunk) HIP_TRY(hipMemcpyAsync(img[0], img[0] + (size_t)n * L.stride[0], L.stride[0], hipMemcpyDeviceToDevice, s));
+    }
+    // the state the next call starts from: the last crop with its pyramid (derivatives are built by the call that tracks from it)
+    for (int l = 0; l <= max_level; ++l) {
+        uint8_t *dst = nullptr;
+        if ((rc = flow_side_buf(fs, cur_side, "pyr", l, L.stride[l], (void **)&dst, err)) < 0) return fail(rc, "%s", err.c_str());
+        HIP_TRY(hipMemcpyAsync(dst, img[l] + (size_t)last * L.stride[l], L.stride[l], hipMemcpyDeviceToDevice, s));
+    }
+    std::vector<float> res(4 * (size_t)N);
+    HIP_TRY(hipMemcpyAsync(res.data(), d_res, sizeof(float) * 4 * (size_t)N, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    for (int i = 0; i < N; ++i) { mean_xy_host[2 * i] = res[4 * i]; mean_xy_host[2 * i + 1] = res[4 * i + 1]; n_good_host[i] = (int)res[4 * i + 2]; }
+    fs.pyr_levels[cur_side] = max_level; fs.deriv_levels[cur_side] = -1;
+    fs.npts = n_good_host[N - 1];
+    fs.flip ^= 1;
+    return RM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // developer build only (-DRM_TRACE, librespmon_hip_trace.so; tools/trace_tail.py): workgroup timelines
 // ------------------------------------------------------------------------------------------
 
