@@ -45,7 +45,7 @@ extern "C" {
 #define RM_F32 2 /* float, widened exactly */
 #define RM_F64 3 /* double: the reference's calibration_buffer dtype (base.py:119-120) */
 /* Frame BUFFERS only -- the `frames` argument of rm_calibrate, rm_locate, rm_locate_submit, rm_locate_streams, rm_locate_sharded,
- * rm_shard_pyramid and rm_eulerian_magnification_bandpass: [T,H,W,3] uint8 in cv2.VideoCapture's channel order.  The kernels apply
+ * rm_shard_pyramid, rm_eulerian_magnification_bandpass and rm_magnify: [T,H,W,3] uint8 in cv2.VideoCapture's channel order.  The kernels apply
  * base.py:230-231 (cv2.cvtColor(BGR2GRAY), then uint8_to_float) as they read the buffer: results are bit-identical to the same call on
  * the RM_U8 buffer that rm_bgr_to_gray makes of it.  Every other entry point takes gray frames and answers RM_E_BADARG. */
 #define RM_BGR8 4
@@ -141,6 +141,25 @@ int rm_eulerian_magnification_bandpass(rm_ctx *ctx, const void *frames_dev, int 
                                        double fps, double freq_min, double freq_max, double amplification,
                                        int pyramid_levels, int skip_levels_at_top, double threshold,
                                        double *masked_dev, double *raw_dev, double *minmax_host, void *stream);
+
+/* ---- the magnified video: original frames plus the amplified band-passed motion ------- */
+/* transforms.py:170 adds the band-passed levels into the video's Laplacian pyramid; the collapse of that pyramid is the commented
+ * line transforms.py:181.  In exact arithmetic that collapse is frame + raw (a frame's Laplacian pyramid telescopes back to the
+ * frame); this entry forms
+ *     m[t] = f[t] + raw[t]                 one float64 addition per pixel
+ * with f[t] the frame as the calibration reads it (RM_U8: k * (1./255); RM_BGR8: cvtColor first) and raw[t] the raw_dev of
+ * rm_eulerian_magnification_bandpass for the same arguments, bit for bit -- in one pass over the frame buffer, without a [T,H,W]
+ * float64 intermediate (1 <= skip_levels_at_top <= 4; other depths materialise raw's unique frames in the workspace first).
+ * out_dev[T,H,W] of out_dtype:  RM_F64: m;  RM_F32: (float)m, round to nearest;  RM_U8: m clamped to [0, 1], then
+ * rm_float_to_uint8's rule (transforms.py:26-29: the C truncation of m * 255; NaN -> 0).  The clamp is this library's: the
+ * reference has no writer for this video, and without it a pixel pushed outside [0, 1] would wrap around modulo 256.
+ * skip_levels_at_top >= pyramid_levels - 1 (nothing is filtered): raw is zero and the output is f converted.
+ * RM_E_BADARG: any other out_dtype, out_dev overlapping the frame buffer, NULL pointers, T < 1;  RM_E_UNSUPPORTED: T > 4096 as
+ * in rm_calibrate.  Asynchronous on `stream`. */
+int rm_magnify(rm_ctx *ctx, const void *frames_dev, int dtype, int T, int H, int W,
+               double fps, double freq_min, double freq_max, double amplification,
+               int pyramid_levels, int skip_levels_at_top,
+               void *out_dev, int out_dtype, void *stream);
 
 /* ---- the fused calibration path: base.py:555-562 (eulerian ... np.average(op, axis=0)) -- */
 /* Reads the frame buffer once; never materialises a [T,H,W] intermediate.  heatmap_dev[H*W]

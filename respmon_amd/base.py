@@ -638,6 +638,15 @@ class RespiratoryMonitor:
 
     calibrate = locate  # north_star names a calibrate(); the reference's calibration entry is locate()
 
+    def magnified_calibration_video(self, out_dtype=None):
+        """The current calibration buffer with its breathing motion amplified -- what locate() looks at, frame by frame: the frames plus
+        the band-passed signal of locate()'s defaults (amplification 500, pyramid_levels 9, skip_levels_at_top 4) at the monitor's fps,
+        freq_min and freq_max (transforms.eulerian_magnification_video).  A device tensor [T,H,W]; `out_dtype` None: uint8 for a uint8 or
+        'bgr8' buffer, float64 otherwise."""
+        from .transforms import eulerian_magnification_video
+        return eulerian_magnification_video(self.calibration_buffer, self.fps, self.freq_min, self.freq_max, 500,
+                                            pyramid_levels=9, skip_levels_at_top=4, out_dtype=out_dtype)
+
     # ------------------------------------------------------------------ state machine
     def run(self):
         """base.py:409-513.  Frame accounting: frame 0 is consumed by 'initialize', the next

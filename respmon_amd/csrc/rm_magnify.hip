@@ -1,0 +1,106 @@
+// respmon_amd/csrc/rm_magnify.hip -- rm_magnify: the magnified video, frames + band-passed motion, in one fused pass (rm_magnify.h;
+// transforms.py:170 adds the band-passed levels into the video pyramid, transforms.py:181 is the commented-out collapse of it)
+// (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
+#include "rm_internal.h"
+#include "rm_magnify.h"
+
+using namespace rm;
+
+namespace {
+
+struct MagCall {
+    const void *frames; void *out;
+    int T, H, W;
+    hipStream_t s;
+};
+
+template <int S, typename Tin, typename Tout>
+int launch_fused(const MagCall &c, const double *cS, const ChainGeom &g)
+{
+    using G = MagGeom<Tin, Tout>;
+    const int ntiles = g.tiles_x * g.tiles_y, nchunks = (sym_frames(c.T) + MAG_FC - 1) / MAG_FC;
+    const int vec = ((((uintptr_t)c.frames | (uintptr_t)c.out) & 15) == 0 && c.W % G::V == 0) ? 1 : 0;
+    hipLaunchKernelGGL((k_magnify<S, Tin, Tout>), dim3((unsigned)(ntiles * nchunks)), dim3(64), sizeof(double) * MAG_LDS_DOUBLES, c.s, cS, g, c.T, ntiles,
+                       (const Tin *)c.frames, (Tout *)c.out, vec);
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
+template <typename Tin, typename Tout>
+int launch_any(const MagCall &c, const double *cS, const ChainGeom *g, const double *raw)
+{
+    if (g) {
+        switch (g->S) {
+        case 1: return launch_fused<1, Tin, Tout>(c, cS, *g);
+        case 2: return launch_fused<2, Tin, Tout>(c, cS, *g);
+        case 3: return launch_fused<3, Tin, Tout>(c, cS, *g);
+        default: return launch_fused<4, Tin, Tout>(c, cS, *g);
+        }
+    }
+    const size_t npix = (size_t)c.H * c.W;
+    hipLaunchKernelGGL((k_magnify_plain<Tin, Tout>), dim3(nblk(npix, 256, 4096), (unsigned)c.T), dim3(256), 0, c.s, (const Tin *)c.frames, raw, c.T, npix,
+                       (Tout *)c.out);
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
+template <typename Tin>
+int launch_out(const MagCall &c, int out_dtype, const double *cS, const ChainGeom *g, const double *raw)
+{
+    switch (out_dtype) {
+    case RM_U8: return launch_any<Tin, uint8_t>(c, cS, g, raw);
+    case RM_F32: return launch_any<Tin, float>(c, cS, g, raw);
+    default: return launch_any<Tin, double>(c, cS, g, raw);
+    }
+}
+
+int launch_in(const MagCall &c, int dtype, int out_dtype, const double *cS, const ChainGeom *g, const double *raw)
+{
+    switch (dtype) {
+    case RM_U8: return launch_out<uint8_t>(c, out_dtype, cS, g, raw);
+    case RM_F16: return launch_out<__half>(c, out_dtype, cS, g, raw);
+    case RM_F32: return launch_out<float>(c, out_dtype, cS, g, raw);
+    case RM_F64: return launch_out<double>(c, out_dtype, cS, g, raw);
+    default: return launch_out<bgr8_t>(c, out_dtype, cS, g, raw);
+    }
+}
+
+}  // namespace
+
+extern "C" int rm_magnify(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, double fps, double fmin, double fmax, double amp,
+                          int levels, int skip, void *out, int out_dtype, void *stream)
+{
+    if (!ctx || !frames || !out || T < 1 || H < 1 || W < 1 || levels < 1 || skip < 0 || !(fps > 0) || !valid_buffer_dtype(dtype))
+        return fail(RM_E_BADARG, "rm_magnify: bad argument");
+    if (out_dtype != RM_U8 && out_dtype != RM_F32 && out_dtype != RM_F64)
+        return fail(RM_E_BADARG, "rm_magnify: out_dtype %d (RM_U8, RM_F32 or RM_F64)", out_dtype);
+    if (T > MAX_T) return fail(RM_E_UNSUPPORTED, "rm_magnify: T=%d > %d", T, MAX_T);
+    const size_t n = (size_t)T * H * W;
+    {
+        const uintptr_t a0 = (uintptr_t)frames, a1 = a0 + n * dtype_size(dtype), b0 = (uintptr_t)out, b1 = b0 + n * dtype_size(out_dtype);
+        if (a0 < b1 && b0 < a1) return fail(RM_E_BADARG, "rm_magnify: out_dev overlaps the frame buffer");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    RM_TRY(ctx_stream_ok(ctx, stream, __func__));
+    const MagCall c{frames, out, T, H, W, s};
+    SmallLevels sl;
+    RM_TRY(front_half(ctx, frames, dtype, T, H, W, fps, fmin, fmax, amp, levels, skip, 0, sl, s));
+    if (sl.all_zero) return launch_in(c, dtype, out_dtype, nullptr, nullptr, nullptr);   // nothing is filtered: raw == 0
+    const int Th = sym_frames(T);
+    if (sl.S >= 1 && sl.S <= 4) {
+        ChainGeom g;
+        RM_TRY(make_geom(sl, g));
+        if (tile_eval_ok(g) && (long long)g.tiles_x * g.tiles_y * ((Th + MAG_FC - 1) / MAG_FC) < (1ll << 31))
+            return launch_in(c, dtype, out_dtype, sl.cS, &g, nullptr);
+    }
+    // every other shape: the materialised collapse of the unique frames (as rm_eulerian_magnification_bandpass forms raw), then the sum
+    const double *cur = sl.cS;
+    for (int l = sl.S - 1; l >= 0; --l) {
+        double *dst = nullptr;
+        RM_TRY(ws(ctx, l == 0 ? "magnify_raw" : ((l & 1) ? "collapse_a" : "collapse_b"), (size_t)Th * sl.h[l] * sl.w[l], &dst));
+        RM_TRY(launch_pyr_up(cur, Th, sl.h[l + 1], sl.w[l + 1], dst, sl.h[l], sl.w[l], 0, nullptr, s));
+        cur = dst;
+    }
+    return launch_in(c, dtype, out_dtype, nullptr, nullptr, cur);
+}

@@ -178,6 +178,34 @@ def eulerian_magnification_bandpass(vid_data, fps, freq_min, freq_max, amplifica
     return device.like_input(masked, vid_data), device.like_input(raw, vid_data)
 
 
+def eulerian_magnification_video(vid_data, fps, freq_min, freq_max, amplification,
+                                 pyramid_levels=4, skip_levels_at_top=2, out_dtype=None):
+    """The magnified video the reference computes and leaves unused: transforms.py:170 adds the band-passed levels into the video's own
+    Laplacian pyramid, transforms.py:181 is the commented-out collapse of it.  [T,H,W] = frame + raw_bandpassed_data (what
+    eulerian_magnification_bandpass returns second), one float64 addition per pixel, formed in one fused pass over the frame buffer
+    (rm_magnify) without a [T,H,W] float64 intermediate.
+    `vid_data`: [T,H,W] uint8 / float16 / float32 / float64 or [T,H,W,3] uint8 BGR; numpy in -> numpy out, device tensor in -> device
+    tensor out.  `out_dtype`: 'uint8' (clamped to [0, 1] first, then float_to_uint8's truncation -- the clamp is this library's),
+    'float32' or 'float64' (numpy / torch dtypes are accepted too); None: uint8 for uint8 and BGR input, float64 otherwise."""
+    t = device.require_gpu()
+    lib = _capi.load()
+    vid = device.to_device(vid_data)
+    T, H, W = device.buffer_shape(vid)
+    code = device.buffer_dtype_code(vid)
+    if out_dtype is None:
+        out_dtype = "uint8" if vid.dtype == t.uint8 else "float64"
+    name = str(out_dtype).replace("torch.", "").replace("numpy.", "")
+    name = getattr(out_dtype, "__name__", name)
+    table = {"uint8": (t.uint8, _capi.RM_U8), "float32": (t.float32, _capi.RM_F32), "float64": (t.float64, _capi.RM_F64)}
+    if name not in table:
+        raise TypeError("out_dtype must be uint8, float32 or float64, got %r" % (out_dtype,))
+    out = t.empty((T, H, W), dtype=table[name][0], device=vid.device)
+    _capi.check(lib, lib.rm_magnify(device.ctx(), device.ptr(vid), code, T, H, W, float(fps), float(freq_min), float(freq_max),
+                                    float(amplification), int(pyramid_levels), int(skip_levels_at_top), device.ptr(out), table[name][1],
+                                    device.stream_ptr()), "rm_magnify")
+    return device.like_input(out, vid_data)
+
+
 def butter_lowpass_filter(data, cutoff, fs, order=5):
     """reference transforms.py:58-69 (used by measure(), base.py:342): 128-sample 1-D signal, host scipy."""
     from scipy.signal import butter, filtfilt
