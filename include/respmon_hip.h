@@ -161,6 +161,28 @@ int rm_magnify(rm_ctx *ctx, const void *frames_dev, int dtype, int T, int H, int
                int pyramid_levels, int skip_levels_at_top,
                void *out_dev, int out_dtype, void *stream);
 
+/* ---- the magnified video in colour: BGR frames in, BGR video out ------------------------ */
+/* For every frame t, pixel p and channel c of an RM_BGR8 frame buffer
+ *     out[t,p,c] = u8( clamp01( (double)frames[t,p,c] * (1./255)  +  raw[t,p] ) )
+ * with raw the raw_dev of rm_eulerian_magnification_bandpass on the same RM_BGR8 buffer with the same arguments, bit for bit (the
+ * band-passed motion of the gray image cvtColor makes of the frame, as everywhere else), and clamp01 / u8 those of rm_magnify's
+ * RM_U8 output: the clamp to [0, 1], then rm_float_to_uint8's C truncation of m * 255.  One float64 multiplication, one addition
+ * and one multiplication per channel, each rounded once.
+ * The same raw goes onto all three channels: cvtColor's weights (0.114, 0.587, 0.299) are the Y row of YIQ, and in the YIQ -> RGB
+ * matrix the Y column is (1, 1, 1), so adding raw to B, G and R is the classical magnification of luma with chroma left alone.
+ *   - A buffer whose three channels are equal yields three equal output channels, each equal to rm_magnify(..., RM_U8) on that
+ *     buffer bit for bit (the gray value of (k, k, k) under the integer cvtColor is k).
+ *   - skip_levels_at_top >= pyramid_levels - 1 (nothing is filtered): raw is zero and every byte k becomes u8(k * (1./255)), the
+ *     reference's float_to_uint8(uint8_to_float(k)): one level below k on 24 of the 256 levels.  This is the rule of the gray
+ *     path, kept for consistency; it is NOT an identity copy.
+ * One pass over the frame buffer as rm_magnify (no [T,H,W] or [T,H,W,3] float64 array for 1 <= skip_levels_at_top <= 4).
+ * RM_E_BADARG: NULL pointers, T, H or W < 1, pyramid_levels < 1, skip_levels_at_top < 0, fps not > 0, out_dev overlapping the
+ * frame buffer (3*T*H*W bytes on both sides);  RM_E_UNSUPPORTED: T > 4096.  Asynchronous on `stream`. */
+int rm_magnify_bgr(rm_ctx *ctx, const uint8_t *frames_dev /* [T,H,W,3] BGR */, int T, int H, int W,
+                   double fps, double freq_min, double freq_max, double amplification,
+                   int pyramid_levels, int skip_levels_at_top,
+                   uint8_t *out_dev /* [T,H,W,3] BGR */, void *stream);
+
 /* ---- the fused calibration path: base.py:555-562 (eulerian ... np.average(op, axis=0)) -- */
 /* Reads the frame buffer once; never materialises a [T,H,W] intermediate.  heatmap_dev[H*W]
  * receives np.average(masked, axis=0) (sequential-in-t float64 sum / T).  minmax_host (may be

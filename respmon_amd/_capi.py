@@ -66,6 +66,7 @@ SIGNATURES = {
     "rm_threshold_mask": (_i, [_vp, _vp, _sz, _d, _vp, _vp, _vp]),
     "rm_eulerian_magnification_bandpass": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _d, _vp, _vp, _vp, _vp]),
     "rm_magnify": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _vp, _i, _vp]),
+    "rm_magnify_bgr": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _d, _d, _i, _i, _vp, _vp]),
     "rm_calibrate": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _d, _u, _vp, _vp, _vp]),
     "rm_heatmap_to_roi": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rm_heat_sparse_packet_doubles": (_sz, [_i]),

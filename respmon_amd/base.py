@@ -638,14 +638,18 @@ class RespiratoryMonitor:
 
     calibrate = locate  # north_star names a calibrate(); the reference's calibration entry is locate()
 
-    def magnified_calibration_video(self, out_dtype=None):
+    def magnified_calibration_video(self, out_dtype=None, color=False):
         """The current calibration buffer with its breathing motion amplified -- what locate() looks at, frame by frame: the frames plus
         the band-passed signal of locate()'s defaults (amplification 500, pyramid_levels 9, skip_levels_at_top 4) at the monitor's fps,
         freq_min and freq_max (transforms.eulerian_magnification_video).  A device tensor [T,H,W]; `out_dtype` None: uint8 for a uint8 or
-        'bgr8' buffer, float64 otherwise."""
+        'bgr8' buffer, float64 otherwise.  `color=True` (buffer_dtype 'bgr8' only): the frames as captured with that motion laid over
+        them, [T,H,W,3] uint8 BGR."""
         from .transforms import eulerian_magnification_video
+        if color and not device.is_bgr_buffer(self.calibration_buffer):
+            raise ValueError("magnified_calibration_video(color=True) needs buffer_dtype='bgr8'; this monitor's buffer_dtype is %r"
+                             % (getattr(self, "buffer_dtype", str(self.calibration_buffer.dtype).replace("torch.", "")),))
         return eulerian_magnification_video(self.calibration_buffer, self.fps, self.freq_min, self.freq_max, 500,
-                                            pyramid_levels=9, skip_levels_at_top=4, out_dtype=out_dtype)
+                                            pyramid_levels=9, skip_levels_at_top=4, out_dtype=out_dtype, color=color)
 
     # ------------------------------------------------------------------ state machine
     def run(self):

@@ -13,7 +13,7 @@
 //   rm_locate.hip         rm_locate, rm_locate_submit / rm_locate_result                 (base.py:547-601)
 //   rm_comm.hip           RCCL behind the C-ABI                                          
 //   rm_motion.hip         ROI mean / crop, corners, LK, PCA                              (base.py:354-407)
-//   rm_magnify.hip        rm_magnify: frames + band-passed motion in one pass            (transforms.py:170, 181; rm_magnify.h)
+//   rm_magnify.hip        rm_magnify, rm_magnify_bgr: frames + band-passed motion in one pass            (transforms.py:170, 181; rm_magnify.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
 // Every kernel header is included by every unit; non-template kernels are `static`, so a unit generates code only for the kernels
 // it launches.

@@ -21,6 +21,20 @@
 //     of size [T, H, W] exists.  The frame tiles are requested before the evaluation starts, so they travel while it runs.
 //   * k_magnify_plain<Tin, Tout>: the same sum behind a materialised raw (skip 0, skip 5 and deeper, images too small for TileEval),
 //     and the conversion alone where nothing is filtered (raw == 0).
+//
+// In colour (rm_magnify_bgr: Tin = Tout = bgr8_t, BGR frames in, BGR video out), for every channel c of pixel p:
+//
+//   out[t, p, c] = u8(clamp01((double)frames[t, p, c] * (1./255) + raw[t, p]))      clamp01, u8: mag_out<uint8_t> below
+//
+// raw is the band-passed motion of the gray image cvtColor makes of the frame, as everywhere else, and the SAME raw goes onto all three
+// channels: cvtColor's weights (0.114, 0.587, 0.299) are the Y row of YIQ, and in the YIQ -> RGB matrix the Y column is (1, 1, 1), so
+// adding raw to B, G and R is the classical magnification of luma with chroma left alone.  One float64 multiplication, one addition
+// and one multiplication per channel, each rounded once.  Both kernels have that instance: k_magnify keeps a lane's 16 pixels packed
+// as loaded (three 16-byte pieces per served frame, 2 x 48 bytes in flight) and widens a byte only when the raw values are at hand.
+//   - three equal channels in give three equal channels out, each the RM_U8 output of rm_magnify on that buffer bit for bit (the
+//     integer cvtColor of (k, k, k) is k);
+//   - where nothing is filtered (skip >= levels - 1) raw is zero and a byte k becomes u8(k * (1./255)): the reference's
+//     float_to_uint8(uint8_to_float(k)), which is k - 1 on 24 of the 256 levels.  NOT an identity copy: the rule of the gray path, kept.
 #pragma once
 
 namespace rm {
@@ -84,8 +98,59 @@ template <typename Tin, typename Tout> struct MagGeom {
     static constexpr int NE = V * C;                       // storage elements of a lane's pixels
 };
 
+template <> struct MagGeom<bgr8_t, bgr8_t> {   // colour: 16 pixels = 48 bytes per lane on both sides, one pass per tile
+    using E = uint8_t;
+    static constexpr int C = 3, V = 16, NP = CT_H * CT_W / (64 * V), NE = V * C;
+};
+template <typename Tin, typename Tout> constexpr bool mag_colour = false;
+template <> constexpr bool mag_colour<bgr8_t, bgr8_t> = true;
+
 // the V pixels of one lane and pass, as stored
 template <typename Tin, typename Tout> struct MagIn { typename MagGeom<Tin, Tout>::E e[MagGeom<Tin, Tout>::NE]; };
+template <> struct MagIn<bgr8_t, bgr8_t> { uint32_t w[MagGeom<bgr8_t, bgr8_t>::NE / 4]; };   // ... kept packed: byte j is bits 8 (j % 4) .. of w[j / 4]
+typedef RM_VEC(uint32_t, 4) MagU32x4;
+
+// the colour form of the two functions below: the lane's 48 bytes as 12 dwords
+template <bool VEC>
+__device__ __forceinline__ void mag_load_bgr(const uint8_t *pe, int nvalid, MagIn<bgr8_t, bgr8_t> &in)
+{
+    constexpr int NE = MagGeom<bgr8_t, bgr8_t>::NE;
+    if constexpr (VEC) {
+#pragma unroll
+        for (int k = 0; k < NE / 16; ++k) {
+            const MagU32x4 v = __builtin_nontemporal_load(reinterpret_cast<const MagU32x4 *>(pe) + k);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) in.w[4 * k + i] = v[i];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NE / 4; ++k) in.w[k] = 0;
+#pragma unroll
+        for (int j = 0; j < NE; ++j) if (j / 3 < nvalid) in.w[j >> 2] |= (uint32_t)pe[j] << (8 * (j & 3));
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void mag_store_bgr(uint8_t *po, int nvalid, const MagIn<bgr8_t, bgr8_t> &in, const double *raw)
+{
+    constexpr int NE = MagGeom<bgr8_t, bgr8_t>::NE;
+    uint32_t o[NE / 4];
+#pragma unroll
+    for (int k = 0; k < NE / 4; ++k) o[k] = 0;
+#pragma unroll
+    for (int j = 0; j < NE; ++j) {   // byte j: channel j % 3 of pixel j / 3
+        const uint8_t k = (uint8_t)(in.w[j >> 2] >> (8 * (j & 3)));
+        o[j >> 2] |= (uint32_t)mag_out<uint8_t>(MagPx<uint8_t>::widen(&k) + raw[j / 3]) << (8 * (j & 3));
+    }
+    if constexpr (VEC) {
+#pragma unroll
+        for (int k = 0; k < NE / 16; ++k)
+            mag_nt_store(MagU32x4{o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]}, reinterpret_cast<MagU32x4 *>(po) + k);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NE; ++j) if (j / 3 < nvalid) po[j] = (uint8_t)(o[j >> 2] >> (8 * (j & 3)));
+    }
+}
 
 // p: the lane's first pixel; VEC: the chunk is whole and aligned to its size; otherwise `nvalid` pixels exist (the rest read as zero)
 template <typename Tin, typename Tout, bool VEC>
@@ -94,7 +159,9 @@ __device__ __forceinline__ void mag_load(const Tin *p, int nvalid, MagIn<Tin, To
     using G = MagGeom<Tin, Tout>;
     using E = typename G::E;
     const E *pe = reinterpret_cast<const E *>(p);
-    if constexpr (VEC && G::C == 1) {
+    if constexpr (mag_colour<Tin, Tout>) {
+        mag_load_bgr<VEC>(pe, nvalid, in);
+    } else if constexpr (VEC && G::C == 1) {
         typedef RM_VEC(E, G::NE) Vec;
         const Vec v = __builtin_nontemporal_load(reinterpret_cast<const Vec *>(pe));
 #pragma unroll
@@ -118,18 +185,22 @@ template <typename Tin, typename Tout, bool VEC>
 __device__ __forceinline__ void mag_store(Tout *p, int nvalid, const MagIn<Tin, Tout> &in, const double *raw)
 {
     using G = MagGeom<Tin, Tout>;
-    Tout o[G::V];
-#pragma unroll
-    for (int i = 0; i < G::V; ++i) o[i] = mag_out<Tout>(MagPx<Tin>::widen(in.e + i * G::C) + raw[i]);
-    if constexpr (VEC) {
-        typedef RM_VEC(Tout, G::V) Vec;
-        Vec v;
-#pragma unroll
-        for (int i = 0; i < G::V; ++i) v[i] = o[i];
-        mag_nt_store(v, reinterpret_cast<Vec *>(p));
+    if constexpr (mag_colour<Tin, Tout>) {
+        mag_store_bgr<VEC>(reinterpret_cast<uint8_t *>(p), nvalid, in, raw);
     } else {
+        Tout o[G::V];
 #pragma unroll
-        for (int i = 0; i < G::V; ++i) if (i < nvalid) p[i] = o[i];
+        for (int i = 0; i < G::V; ++i) o[i] = mag_out<Tout>(MagPx<Tin>::widen(in.e + i * G::C) + raw[i]);
+        if constexpr (VEC) {
+            typedef RM_VEC(Tout, G::V) Vec;
+            Vec v;
+#pragma unroll
+            for (int i = 0; i < G::V; ++i) v[i] = o[i];
+            mag_nt_store(v, reinterpret_cast<Vec *>(p));
+        } else {
+#pragma unroll
+            for (int i = 0; i < G::V; ++i) if (i < nvalid) p[i] = o[i];
+        }
     }
 }
 
@@ -211,7 +282,7 @@ __global__ __launch_bounds__(64) void k_magnify(const double *cS, ChainGeom g, i
     }
 }
 
-// out[t, p] = convert(f[t, p] + raw[sym_frame(t), p]); raw: the unique frames [T / 2 + 1][npix], or null where nothing is filtered (raw == 0).
+// out[t, p] = convert(f[t, p] + raw[sym_frame(t), p]) (colour: per channel of f[t, p], the header of this file); raw: the unique frames [T / 2 + 1][npix], or null where nothing is filtered (raw == 0).
 // blockIdx.y = t.
 template <typename Tin, typename Tout>
 __global__ __launch_bounds__(256) void k_magnify_plain(const Tin *frames, const double *raw, int T, size_t npix, Tout *out)
@@ -221,8 +292,13 @@ __global__ __launch_bounds__(256) void k_magnify_plain(const Tin *frames, const 
     const double *r = raw ? raw + (size_t)sym_frame(t, T) * npix : nullptr;
     Tout *o = out + (size_t)t * npix;
     for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (size_t)gridDim.x * 256) {
-        const double fv = MagPx<Tin>::widen(reinterpret_cast<const typename MagPx<Tin>::E *>(f + p));
-        o[p] = mag_out<Tout>(fv + (r ? r[p] : 0.0));
+        const typename MagPx<Tin>::E *e = reinterpret_cast<const typename MagPx<Tin>::E *>(f + p);
+        const double rv = r ? r[p] : 0.0;
+        if constexpr (mag_colour<Tin, Tout>)
+            o[p] = bgr8_t{mag_out<uint8_t>(MagPx<uint8_t>::widen(e) + rv), mag_out<uint8_t>(MagPx<uint8_t>::widen(e + 1) + rv),
+                          mag_out<uint8_t>(MagPx<uint8_t>::widen(e + 2) + rv)};
+        else
+            o[p] = mag_out<Tout>(MagPx<Tin>::widen(e) + rv);
     }
 }
 

@@ -1,4 +1,4 @@
-// respmon_amd/csrc/rm_magnify.hip -- rm_magnify: the magnified video, frames + band-passed motion, in one fused pass (rm_magnify.h;
+// respmon_amd/csrc/rm_magnify.hip -- rm_magnify, rm_magnify_bgr: the magnified video, frames + band-passed motion, in one fused pass (rm_magnify.h;
 // transforms.py:170 adds the band-passed levels into the video pyramid, transforms.py:181 is the commented-out collapse of it)
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
@@ -65,6 +65,38 @@ int launch_in(const MagCall &c, int dtype, int out_dtype, const double *cS, cons
     }
 }
 
+// behind front_half(): launch(cS, geometry, raw) with nothing filtered (all null: raw == 0), the level-S signal and the geometry of
+// the fused kernel (1 <= S <= 4 where TileEval applies), or the materialised unique frames of raw
+template <typename Launch>
+int magnify_dispatch(rm_ctx *ctx, const MagCall &c, int dtype, double fps, double fmin, double fmax, double amp, int levels, int skip, Launch launch)
+{
+    SmallLevels sl;
+    RM_TRY(front_half(ctx, c.frames, dtype, c.T, c.H, c.W, fps, fmin, fmax, amp, levels, skip, 0, sl, c.s));
+    if (sl.all_zero) return launch(nullptr, nullptr, nullptr);   // nothing is filtered: raw == 0
+    const int Th = sym_frames(c.T);
+    if (sl.S >= 1 && sl.S <= 4) {
+        ChainGeom g;
+        RM_TRY(make_geom(sl, g));
+        if (tile_eval_ok(g) && (long long)g.tiles_x * g.tiles_y * ((Th + MAG_FC - 1) / MAG_FC) < (1ll << 31))
+            return launch(sl.cS, &g, nullptr);
+    }
+    // every other shape: the materialised collapse of the unique frames (as rm_eulerian_magnification_bandpass forms raw), then the sum
+    const double *cur = sl.cS;
+    for (int l = sl.S - 1; l >= 0; --l) {
+        double *dst = nullptr;
+        RM_TRY(ws(ctx, l == 0 ? "magnify_raw" : ((l & 1) ? "collapse_a" : "collapse_b"), (size_t)Th * sl.h[l] * sl.w[l], &dst));
+        RM_TRY(launch_pyr_up(cur, Th, sl.h[l + 1], sl.w[l + 1], dst, sl.h[l], sl.w[l], 0, nullptr, c.s));
+        cur = dst;
+    }
+    return launch(nullptr, nullptr, cur);
+}
+
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
+    return a0 < b1 && b0 < a1;
+}
+
 }  // namespace
 
 extern "C" int rm_magnify(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, double fps, double fmin, double fmax, double amp,
@@ -76,31 +108,25 @@ extern "C" int rm_magnify(rm_ctx *ctx, const void *frames, int dtype, int T, int
         return fail(RM_E_BADARG, "rm_magnify: out_dtype %d (RM_U8, RM_F32 or RM_F64)", out_dtype);
     if (T > MAX_T) return fail(RM_E_UNSUPPORTED, "rm_magnify: T=%d > %d", T, MAX_T);
     const size_t n = (size_t)T * H * W;
-    {
-        const uintptr_t a0 = (uintptr_t)frames, a1 = a0 + n * dtype_size(dtype), b0 = (uintptr_t)out, b1 = b0 + n * dtype_size(out_dtype);
-        if (a0 < b1 && b0 < a1) return fail(RM_E_BADARG, "rm_magnify: out_dev overlaps the frame buffer");
-    }
-    hipStream_t s = (hipStream_t)stream;
+    if (ranges_overlap(frames, n * dtype_size(dtype), out, n * dtype_size(out_dtype))) return fail(RM_E_BADARG, "rm_magnify: out_dev overlaps the frame buffer");
     HIP_TRY(hipSetDevice(ctx->device));
     RM_TRY(ctx_stream_ok(ctx, stream, __func__));
-    const MagCall c{frames, out, T, H, W, s};
-    SmallLevels sl;
-    RM_TRY(front_half(ctx, frames, dtype, T, H, W, fps, fmin, fmax, amp, levels, skip, 0, sl, s));
-    if (sl.all_zero) return launch_in(c, dtype, out_dtype, nullptr, nullptr, nullptr);   // nothing is filtered: raw == 0
-    const int Th = sym_frames(T);
-    if (sl.S >= 1 && sl.S <= 4) {
-        ChainGeom g;
-        RM_TRY(make_geom(sl, g));
-        if (tile_eval_ok(g) && (long long)g.tiles_x * g.tiles_y * ((Th + MAG_FC - 1) / MAG_FC) < (1ll << 31))
-            return launch_in(c, dtype, out_dtype, sl.cS, &g, nullptr);
-    }
-    // every other shape: the materialised collapse of the unique frames (as rm_eulerian_magnification_bandpass forms raw), then the sum
-    const double *cur = sl.cS;
-    for (int l = sl.S - 1; l >= 0; --l) {
-        double *dst = nullptr;
-        RM_TRY(ws(ctx, l == 0 ? "magnify_raw" : ((l & 1) ? "collapse_a" : "collapse_b"), (size_t)Th * sl.h[l] * sl.w[l], &dst));
-        RM_TRY(launch_pyr_up(cur, Th, sl.h[l + 1], sl.w[l + 1], dst, sl.h[l], sl.w[l], 0, nullptr, s));
-        cur = dst;
-    }
-    return launch_in(c, dtype, out_dtype, nullptr, nullptr, cur);
+    const MagCall c{frames, out, T, H, W, (hipStream_t)stream};
+    return magnify_dispatch(ctx, c, dtype, fps, fmin, fmax, amp, levels, skip,
+                            [&](const double *cS, const ChainGeom *g, const double *raw) { return launch_in(c, dtype, out_dtype, cS, g, raw); });
+}
+
+// the colour form: BGR frames in, BGR video out, the same raw onto the three channels (rm_magnify.h)
+extern "C" int rm_magnify_bgr(rm_ctx *ctx, const uint8_t *frames, int T, int H, int W, double fps, double fmin, double fmax, double amp, int levels,
+                              int skip, uint8_t *out, void *stream)
+{
+    if (!ctx || !frames || !out || T < 1 || H < 1 || W < 1 || levels < 1 || skip < 0 || !(fps > 0)) return fail(RM_E_BADARG, "rm_magnify_bgr: bad argument");
+    if (T > MAX_T) return fail(RM_E_UNSUPPORTED, "rm_magnify_bgr: T=%d > %d", T, MAX_T);
+    const size_t n = (size_t)T * H * W * sizeof(bgr8_t);
+    if (ranges_overlap(frames, n, out, n)) return fail(RM_E_BADARG, "rm_magnify_bgr: out_dev overlaps the frame buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    RM_TRY(ctx_stream_ok(ctx, stream, __func__));
+    const MagCall c{frames, out, T, H, W, (hipStream_t)stream};
+    return magnify_dispatch(ctx, c, RM_BGR8, fps, fmin, fmax, amp, levels, skip,
+                            [&](const double *cS, const ChainGeom *g, const double *raw) { return launch_any<bgr8_t, bgr8_t>(c, cS, g, raw); });
 }

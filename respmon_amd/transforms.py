@@ -179,23 +179,39 @@ def eulerian_magnification_bandpass(vid_data, fps, freq_min, freq_max, amplifica
 
 
 def eulerian_magnification_video(vid_data, fps, freq_min, freq_max, amplification,
-                                 pyramid_levels=4, skip_levels_at_top=2, out_dtype=None):
+                                 pyramid_levels=4, skip_levels_at_top=2, out_dtype=None, color=False):
     """The magnified video the reference computes and leaves unused: transforms.py:170 adds the band-passed levels into the video's own
     Laplacian pyramid, transforms.py:181 is the commented-out collapse of it.  [T,H,W] = frame + raw_bandpassed_data (what
     eulerian_magnification_bandpass returns second), one float64 addition per pixel, formed in one fused pass over the frame buffer
     (rm_magnify) without a [T,H,W] float64 intermediate.
     `vid_data`: [T,H,W] uint8 / float16 / float32 / float64 or [T,H,W,3] uint8 BGR; numpy in -> numpy out, device tensor in -> device
     tensor out.  `out_dtype`: 'uint8' (clamped to [0, 1] first, then float_to_uint8's truncation -- the clamp is this library's),
-    'float32' or 'float64' (numpy / torch dtypes are accepted too); None: uint8 for uint8 and BGR input, float64 otherwise."""
+    'float32' or 'float64' (numpy / torch dtypes are accepted too); None: uint8 for uint8 and BGR input, float64 otherwise.
+    `color=True` (rm_magnify_bgr): `vid_data` must be a [T,H,W,3] uint8 BGR buffer and the result is the [T,H,W,3] uint8 BGR video with
+    the same band-passed motion (that of the gray image) added to the three channels -- luma magnified, chroma left alone; `out_dtype`
+    None or uint8.  The default gives the gray video, also for BGR input."""
     t = device.require_gpu()
     lib = _capi.load()
     vid = device.to_device(vid_data)
     T, H, W = device.buffer_shape(vid)
-    code = device.buffer_dtype_code(vid)
+
+    def dtype_name(d):
+        return getattr(d, "__name__", str(d).replace("torch.", "").replace("numpy.", ""))
+
+    if color:
+        if not device.is_bgr_buffer(vid):
+            raise ValueError("color=True needs a [T,H,W,3] uint8 BGR frame buffer, got %s %s" % (tuple(vid.shape), vid.dtype))
+        if out_dtype is not None and dtype_name(out_dtype) != "uint8":
+            raise TypeError("out_dtype must be None or uint8 with color=True, got %r" % (out_dtype,))
+        out = t.empty_like(vid)
+        _capi.check(lib, lib.rm_magnify_bgr(device.ctx(), device.ptr(vid), T, H, W, float(fps), float(freq_min), float(freq_max),
+                                            float(amplification), int(pyramid_levels), int(skip_levels_at_top), device.ptr(out),
+                                            device.stream_ptr()), "rm_magnify_bgr")
+        return device.like_input(out, vid_data)
     if out_dtype is None:
         out_dtype = "uint8" if vid.dtype == t.uint8 else "float64"
-    name = str(out_dtype).replace("torch.", "").replace("numpy.", "")
-    name = getattr(out_dtype, "__name__", name)
+    name = dtype_name(out_dtype)
+    code = device.buffer_dtype_code(vid)
     table = {"uint8": (t.uint8, _capi.RM_U8), "float32": (t.float32, _capi.RM_F32), "float64": (t.float64, _capi.RM_F64)}
     if name not in table:
         raise TypeError("out_dtype must be uint8, float32 or float64, got %r" % (out_dtype,))
