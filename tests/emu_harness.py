@@ -63,6 +63,22 @@ class Emu:
         self.ck(self.lib.rm_temporal_bandpass_filter_fft(self.ctx, ptr(data), T, npix, fps, fmin, fmax, amp, ptr(out), None), "temporal")
         return out
 
+    def temporal_rc(self, data, fps, fmin, fmax, amp):
+        """the raw return code of rm_temporal_bandpass_filter_fft (a refusal is an answer, not an exception) and the output"""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        out = np.zeros_like(data)
+        rc = self.lib.rm_temporal_bandpass_filter_fft(self.ctx, ptr(data), data.shape[0], data[0].size, fps, fmin, fmax, amp, ptr(out), None)
+        return rc, out
+
+    def magnify(self, frames, fps, fmin, fmax, amp, levels, skip):
+        """rm_magnify with a float64 output"""
+        frames = np.ascontiguousarray(frames)
+        T, H, W, code = buf_args(frames)
+        out = np.empty((T, H, W))
+        self.ck(self.lib.rm_magnify(self.ctx, ptr(frames), code, T, H, W, float(fps), float(fmin), float(fmax), float(amp), int(levels), int(skip),
+                                    ptr(out), _capi.RM_F64, None), "magnify")
+        return out
+
     def lfilter(self, b, a, data, scale=1.0):
         data = np.ascontiguousarray(data, dtype=np.float64)
         T = data.shape[0]
