@@ -243,6 +243,29 @@ int rm_locate_submit(rm_ctx *ctx, const void *frames_dev, int dtype, int T, int 
                      void *stream, int *ticket_host);
 int rm_locate_result(rm_ctx *ctx, int ticket, int32_t *xywh_host);
 
+/* ---- several subjects in one frame: the K largest contours instead of the largest one.  Not a reference function: base.py:571 keeps
+ *      max(contours, key=cv2.contourArea) and drops the rest.  On the image base.py:563-566 builds from the heatmap,
+ *        contours = cv2.findContours(thresh, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)
+ *        keep those with cv2.contourArea(c) >= min_area
+ *        order them by decreasing area; equal areas keep the order of the list findContours returned (the earlier one ranks first:
+ *        a stable sort on -area -- at one entry that is what Python's max() keeps)
+ *      and the first min(max_rois, count) are returned as cv2.boundingRect (xywh_host[i][4]) and area (area_host[i], may be NULL);
+ *      *n_host = how many.  Contours of area 0 (single pixels, one-pixel lines) are contours and are listed when min_area == 0.
+ *      With min_area == 0 entry 0 is the ROI of rm_heatmap_to_roi / rm_locate on the same input; rm_locate_multi with max_rois == 1
+ *      is rm_locate.  rm_set_contour_clip_frame and RM_FLAG_CONTOUR_CLIP_FRAME act as they do there.
+ *      Returns RM_OK (*n_host >= 1) or RM_NO_CONTOUR (*n_host == 0: nothing survives);  RM_E_BADARG: max_rois outside
+ *      1..RM_MAX_ROIS, min_area negative or NaN, NULL xywh_host / n_host, H or W < 1.
+ *      The calls leave the state of the single-ROI stage alone (its pinned result areas, the contour-labelling rule's counters,
+ *      rm_contour_stats): an rm_locate after them behaves as if they had not happened.  One stream wait per call; every external
+ *      border is followed on the host. */
+#define RM_MAX_ROIS 64
+int rm_heatmap_to_rois(rm_ctx *ctx, const double *heatmap_dev, int H, int W, int threshold, int max_rois, double min_area,
+                       int32_t *xywh_host /* [max_rois][4] */, double *area_host /* [max_rois], may be NULL */, int *n_host, void *stream);
+int rm_locate_multi(rm_ctx *ctx, const void *frames_dev, int dtype, int T, int H, int W, double fps,
+                    double freq_min, double freq_max, double amplification, int pyramid_levels,
+                    int skip_levels_at_top, double temporal_threshold, int threshold, unsigned flags,
+                    int max_rois, double min_area, int32_t *xywh_host, double *area_host, int *n_host, void *stream);
+
 /* ---- frame-sharded calibration (one [T,H,W] buffer split by frame index over the GPUs of a node; SURVEY 8e
  *      "Mode A", BASELINE north_star).  Same arithmetic as rm_calibrate (transforms.py:144-198, base.py:562),
  *      cut at the three points where frames meet; the caller runs a collective at each cut
@@ -343,6 +366,13 @@ int rm_roi_mean_clip(rm_ctx *ctx, const void *frames_dev, int dtype, int N, int 
 int rm_flow_clip(rm_ctx *ctx, rm_flow_state *state, const void *frames_dev, int dtype, int N, int H, int W, int x, int y, int w, int h,
                  int win_w, int win_h, int max_level, int max_count, double epsilon, float *mean_xy_host, int *n_good_host, void *stream);
 int rm_pca_reduce_windows(rm_ctx *ctx, const float *motion_host, int n, int first, int window, double *out_host, void *stream);
+/*      rm_roi_mean_multi_clip: K rectangles (rois_host[k] = x, y, w, h; several subjects in one frame) over the clip in one call:
+ *        out_host[i * K + k] = rm_roi_mean of frame i and rectangle k, bit for bit, for every frame dtype.  One launch whatever N and
+ *        K, one result copy, one stream wait.  Rectangles may overlap, repeat, be 1 x 1 or the whole frame.  RM_E_BADARG -- nothing is
+ *        launched, out_host is not written -- for K outside 1..RM_MAX_ROIS, N < 1, or any rectangle that does not lie inside the frame.
+ *        K == 1 equals rm_roi_mean_clip. */
+int rm_roi_mean_multi_clip(rm_ctx *ctx, const void *frames_dev, int dtype, int N, int H, int W,
+                           const int32_t *rois_host /* [K][4] x,y,w,h */, int K, double *out_host /* [N][K] */, void *stream);
 
 /* ---- multi-GPU steps with RCCL behind the C-ABI (the call site they replace is base.py:444, run once per GPU).
  *      One process per GPU, one context per process.  librccl is opened at run time (dlopen), so single-GPU users never need it.

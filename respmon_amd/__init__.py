@@ -10,7 +10,10 @@ def __getattr__(name):
     if name == "RespiratoryMonitor":
         from .base import RespiratoryMonitor
         return RespiratoryMonitor
-    if name in ("transforms", "pyramid", "base", "device", "synth", "dist"):
+    if name == "SubjectTracker":
+        from .subjects import SubjectTracker
+        return SubjectTracker
+    if name in ("transforms", "pyramid", "base", "device", "synth", "dist", "subjects", "measure"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

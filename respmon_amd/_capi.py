@@ -17,6 +17,7 @@ RM_E_UNSUPPORTED = -4
 RM_E_COMM = -6
 RM_E_BUSY = -7
 RM_LOCATE_TICKETS = 2
+RM_MAX_ROIS = 64
 RM_U8, RM_F16, RM_F32, RM_F64 = 0, 1, 2, 3
 RM_BGR8 = 4   # frame buffers only: [T,H,W,3] uint8 in cv2.VideoCapture's channel order (include/respmon_hip.h)
 RM_FLAG_NO_PRUNE = 1
@@ -74,6 +75,8 @@ SIGNATURES = {
     "rm_heat_sparse_merge_roi": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rm_heat_sparse_tiles_needed": (_i, [_vp, _vp]),
     "rm_locate": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _d, _i, _u, _vp, _vp]),
+    "rm_heatmap_to_rois": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _vp, _vp, _c.POINTER(_i), _vp]),
+    "rm_locate_multi": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _d, _i, _u, _i, _d, _vp, _vp, _c.POINTER(_i), _vp]),
     "rm_locate_submit": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _d, _i, _u, _vp, _vp]),
     "rm_locate_result": (_i, [_vp, _i, _vp]),
     "rm_shard_layout": (_i, [_i, _i, _i, _i, _c.POINTER(_sz)]),
@@ -94,6 +97,7 @@ SIGNATURES = {
     "rm_mean_flow": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "rm_pca_reduce": (_i, [_vp, _vp, _i, _vp, _vp]),
     "rm_roi_mean_clip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "rm_roi_mean_multi_clip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "rm_flow_clip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
     "rm_pca_reduce_windows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "rm_bgr_to_gray": (_i, [_vp, _vp, _sz, _vp, _vp]),

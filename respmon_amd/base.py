@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _capi, device
 from .tools import Benchmarker, reduce_bounding_box
-from .transforms import butter_lowpass_filter
+from .measure import BreathSignal
 
 THRESH_BINARY = 0  # cv2.THRESH_BINARY
 
@@ -114,6 +114,29 @@ class _Backend:
         if rc == _capi.RM_NO_CONTOUR:
             return None
         return xywh[0], xywh[1], xywh[2], xywh[3]
+
+    def locate_multi(self, buf, fps, freq_min=0.1, freq_max=1.0, amplification=500, pyramid_levels=9, skip_levels_at_top=4,
+                     temporal_threshold=0.7, threshold=20, flags=0, max_rois=4, min_area=0.0, with_areas=False):
+        """The `max_rois` largest contours of locate()'s thresholded heat map as a list of (x, y, w, h), largest first (rm_locate_multi);
+        [] where locate() returns None.  with_areas: (rois, areas)."""
+        import ctypes
+        T, H, W = device.buffer_shape(buf)
+        idx = buf.device.index
+        ctx = device._CTX.get(idx) or device.ctx(idx)
+        stream = ctypes.c_void_p(device.raw_stream(idx))
+        cap = max(int(max_rois), 1)
+        xywh = np.zeros((cap, 4), dtype=np.int32)
+        area = np.zeros(cap, dtype=np.float64)
+        n = ctypes.c_int(0)
+        rc = self.lib.rm_locate_multi(ctx, ctypes.c_void_p(buf.data_ptr()), device.buffer_dtype_code(buf), T, H, W,
+                                      float(fps), float(freq_min), float(freq_max), float(amplification),
+                                      int(pyramid_levels), int(skip_levels_at_top), float(temporal_threshold),
+                                      int(threshold), int(flags), int(max_rois), float(min_area),
+                                      ctypes.c_void_p(xywh.ctypes.data), ctypes.c_void_p(area.ctypes.data), ctypes.byref(n), stream)
+        if rc < 0:
+            _capi.check(self.lib, rc, "rm_locate_multi")
+        rois = [tuple(int(v) for v in xywh[i]) for i in range(n.value)]
+        return (rois, [float(a) for a in area[:n.value]]) if with_areas else rois
 
     # -- ingest -----------------------------------------------------------------------
     def bgr_to_gray(self, bgr_u8_host):
@@ -269,6 +292,18 @@ class _Backend:
                                                         ctypes.c_void_p(out.ctypes.data), device.stream_ptr()), "rm_roi_mean_clip")
         return out
 
+    def roi_mean_multi_clip(self, frames, rois):
+        """ndarray [N, K]: the ROI mean of every frame of the resident clip and every rectangle (x, y, w, h) of `rois`, one call."""
+        import ctypes
+        frames = frames.contiguous()
+        N, H, W = frames.shape
+        r = np.ascontiguousarray(rois, dtype=np.int32).reshape(-1, 4)
+        out = np.empty((N, len(r)), dtype=np.float64)
+        _capi.check(self.lib, self.lib.rm_roi_mean_multi_clip(device.ctx(), device.ptr(frames), device.dtype_code(frames), N, H, W,
+                                                              ctypes.c_void_p(r.ctypes.data), len(r), ctypes.c_void_p(out.ctypes.data),
+                                                              device.stream_ptr()), "rm_roi_mean_multi_clip")
+        return out
+
     def flow_clip(self, state, frames, x, y, w, h, winSize, maxLevel, criteria):
         import ctypes
         frames = frames.contiguous()
@@ -295,7 +330,7 @@ class _Backend:
         return out
 
 
-class RespiratoryMonitor:
+class RespiratoryMonitor(BreathSignal):
     CAP_PROP_FRAME_WIDTH, CAP_PROP_FRAME_HEIGHT, CAP_PROP_FPS = 3, 4, 5
     TERM_CRITERIA_COUNT, TERM_CRITERIA_EPS = 1, 2
 
@@ -488,40 +523,8 @@ class RespiratoryMonitor:
     def update_ui(self):
         """base.py:255-297: no UI in this build."""
 
-    # ------------------------------------------------------------------ BPM estimation ("next" row f2)
-    def find_peaks(self):
-        """base.py:312-338 with own restatements of peakutils.indexes / gaussian_fit (peakutils is an
-        un-pinned dependency that is not installable here: parity unpinned)."""
-        from . import peaks
-        width = self.peak_minimum_sample_distance
-        idxs = peaks.indexes(np.asarray(self.filtered_data), min_dist=width)
-        final, fits = [], []
-        t_arr = np.array(self.t)
-        f_arr = np.array(self.filtered_data)
-        for idx in idxs:
-            w = width
-            if idx - width < 0:
-                w = idx
-            if idx + w > len(self.t):
-                w = len(self.t) - idx
-            ti, di = t_arr[idx - w:idx + w], f_arr[idx - w:idx + w]
-            try:
-                params = peaks.gaussian_fit(ti, di)
-                fits.append(0.0)  # the reference's r2 is identically 0 (ssr == sst, base.py:330-332)
-                if params[2] < self.gaussian_cutoff:
-                    final.append(idx)
-            except (RuntimeError, TypeError, ValueError):
-                pass
-        return final, fits
-
-    def measure(self):
-        """base.py:340-352."""
-        self.filtered_data = np.array(butter_lowpass_filter(self.data, self.freq_max * 0.5, self.fps, self.filter_order))
-        self.peak_indices, _fits = self.find_peaks()
-        self.peak_times = np.take(self.t, self.peak_indices)
-        diffs = [a - b for b, a in zip(self.peak_times, self.peak_times[1:])]
-        if len(diffs) > 0:
-            self.freq.append(60.0 / np.mean(diffs))
+    # BPM estimation (find_peaks / measure, base.py:312-352) and the per-frame bookkeeping of the 'measure' state (_pop_full_buffers /
+    # _record_value, base.py:473-497) live in respmon_amd/measure.py BreathSignal, shared with respmon_amd.subjects.SubjectTracker.
 
     # ------------------------------------------------------------------ hot path B
     def extract_motion(self):
@@ -635,6 +638,29 @@ class RespiratoryMonitor:
         if verbose and roi is not None:
             print('x:{0}, y:{1}, w:{2}, h:{3}'.format(*roi))
         return roi
+
+    @staticmethod
+    def locate_all(calibration_video_data, fps,
+                   freq_min=0.1, freq_max=1.0, amplification=500,
+                   pyramid_levels=9, skip_levels_at_top=4, temporal_threshold=0.7,
+                   threshold=20, threshold_type=THRESH_BINARY,
+                   verbose=False, max_rois=4, min_area=0.0):
+        """locate() for a frame that holds several subjects: where base.py:571 keeps max(contours, key=cv2.contourArea), this returns
+        the bounding rectangles of the `max_rois` largest contours with contourArea >= min_area, largest first, as a list of
+        (x, y, w, h) -- empty where locate() returns None.  Equal areas rank in the order of cv2.findContours' list, so with
+        min_area == 0 the first entry is locate()'s ROI.  One calibration pass (rm_locate_multi); not a reference function."""
+        if threshold_type != THRESH_BINARY:
+            raise NotImplementedError("only cv2.THRESH_BINARY is used by the reference (base.py:448,551)")
+        buf = device.to_device(calibration_video_data)
+        rois = _Backend().locate_multi(buf, fps, freq_min, freq_max, amplification, pyramid_levels, skip_levels_at_top,
+                                       temporal_threshold, threshold,
+                                       flags=(_capi.RM_FLAG_CONTOUR_CLIP_FRAME if RespiratoryMonitor.opencv_contours_clip_frame else 0) |
+                                             (_capi.RM_FLAG_FILTER_LAPLACIANS if RespiratoryMonitor.reference_operation_order else 0),
+                                       max_rois=max_rois, min_area=min_area)
+        if verbose:
+            for roi in rois:
+                print('x:{0}, y:{1}, w:{2}, h:{3}'.format(*roi))
+        return rois
 
     calibrate = locate  # north_star names a calibrate(); the reference's calibration entry is locate()
 
@@ -839,25 +865,6 @@ class RespiratoryMonitor:
                 logging.info('Benchmark Report...\r\n' + self.benchmarker.get_report())
                 self.reset()
                 self.state = 'calibration'
-
-    def _pop_full_buffers(self):
-        for b in self.buffers:                                              # base.py:473-475
-            if len(b) >= self.measure_buffer_length:
-                b.popleft()
-
-    def _record_value(self, value):
-        """What the 'measure' state does with the value of one frame (base.py:477-497)."""
-        self.data.append(value)
-        if len(self.t) == 0:
-            self.t.append(0.)
-        else:
-            self.t.append(self.t[-1] + (1. / self.fps))
-        if self.save_all_data:
-            self.all_data.append((self.t[-1], value))
-        if len(self.data) > self.measure_initialization_length:
-            self.measure()
-            if not self.disable_error_detection and self.detect_errors():
-                self.trigger_error("error detection found poor signal")
 
     def _locate_buffer(self):
         """the locate() call of run(), base.py:444-448: threshold = int(round(0.08*255)) = 20; pyramid_levels=9,

@@ -229,7 +229,8 @@ int largest_external_contour(const uint8_t *bin, int H, int W, const uint32_t *r
 //   a run starts a new outer border iff its first pixel is still unmarked and the last marked pixel to its left in
 //   this row is not a SEEN (entering) border, i.e. we are not inside an already traced component (RETR_EXTERNAL);
 //   the "last marked pixel" then moves to the last marked pixel of this run, if it has one.
-static int scan_runs(Tracer &tr, const uint64_t *bits, int H, int W, RoiResult *out, int ya = 0, int yb = -2)
+// `all` (nullable): every border followed is also appended there, in discovery order (ranked_external_contours_bits).
+static int scan_runs(Tracer &tr, const uint64_t *bits, int H, int W, RoiResult *out, int ya = 0, int yb = -2, std::vector<ContourRec> *all = nullptr)
 {
     const int step = tr.step;
     double best = -1.0;
@@ -248,6 +249,7 @@ static int scan_runs(Tracer &tr, const uint64_t *bits, int H, int W, RoiResult *
                 long long a2 = tr.follow(row + a, a + 1, y + 1, minx, miny, maxx, maxy);
                 double area = 0.5 * (double)(a2 < 0 ? -a2 : a2);
                 ++out->n_contours;
+                if (all) all->push_back(ContourRec{minx - 1, miny - 1, maxx - minx + 1, maxy - miny + 1, area});
                 if (area >= best) {
                     best = area;
                     out->found = 1;
@@ -288,6 +290,24 @@ int largest_external_contour_bits(const uint64_t *bits, int H, int W, RoiResult 
     const int rc = scan_runs(g_tracer, bits, H, W, out);
     out->steps = g_tracer.steps;
     return rc;
+}
+
+int ranked_external_contours_bits(const uint64_t *bits, int H, int W, int max_out, double min_area, ContourRec *out, int *n_contours)
+{
+    if (n_contours) *n_contours = 0;
+    if (H <= 0 || W <= 0 || max_out < 1) return 0;
+    Tracer tr;   // (not g_tracer: the single-ROI stage's bookkeeping of touched rows stays what its own last image made it)
+    tr.prepare_bits(bits, H, W);
+    RoiResult single{};
+    std::vector<ContourRec> all;
+    scan_runs(tr, bits, H, W, &single, 0, -2, &all);
+    if (n_contours) *n_contours = single.n_contours;
+    std::reverse(all.begin(), all.end());   // cv2.findContours lists the border discovered last first
+    all.erase(std::remove_if(all.begin(), all.end(), [min_area](const ContourRec &c) { return c.area < min_area; }), all.end());
+    std::stable_sort(all.begin(), all.end(), [](const ContourRec &a, const ContourRec &b) { return a.area > b.area; });
+    const int n = (int)std::min<size_t>(all.size(), (size_t)max_out);
+    for (int i = 0; i < n; ++i) out[i] = all[i];
+    return n;
 }
 
 // One hole-free blob?  If every row of [y0, y1] holds exactly ONE run of foreground and the runs of neighbouring rows touch

@@ -15,6 +15,14 @@ struct RoiResult {
 int largest_external_contour(const uint8_t *bin, int H, int W, const uint32_t *row_any, RoiResult *out);
 // the same on a bit-packed image: bit (p & 63) of word (p >> 6) = pixel p = y*W + x; words beyond H*W bits are not read
 int largest_external_contour_bits(const uint64_t *bits, int H, int W, RoiResult *out);
+// EVERY external contour of the packed image, ranked (rm_heatmap_to_rois): contours with contourArea < min_area are dropped, the rest
+// ordered by decreasing area, equal areas in the order of the list cv2.findContours returns (reverse discovery order: the border the
+// raster scan met later ranks first -- at one entry that is Python's max(), the `area >= best` update of the single-ROI scan).  The
+// first min(max_out, count) go to out[]; returns how many were written, *n_contours (nullable) = contours met before the filter.
+// Works on a tracer of its own: the thread's tracer the functions above keep between calls (its working copy, the rows it has to
+// clean next time) is neither read nor written.
+struct ContourRec { int x, y, w, h; double area; };
+int ranked_external_contours_bits(const uint64_t *bits, int H, int W, int max_out, double min_area, ContourRec *out, int *n_contours);
 // ... when the caller knows that only rows [y0, y1] can hold foreground now or held any in the previous image given to
 // this thread's tracer (y1 < y0: no such row): the other rows are neither read nor cleaned
 int largest_external_contour_bits_rows(const uint64_t *bits, int H, int W, int y0, int y1, RoiResult *out);

@@ -12,7 +12,7 @@
 //   rm_roi.hip            heatmap -> ROI, sparse heatmap packets                         (base.py:563-575)
 //   rm_locate.hip         rm_locate, rm_locate_submit / rm_locate_result                 (base.py:547-601)
 //   rm_comm.hip           RCCL behind the C-ABI                                          
-//   rm_motion.hip         ROI mean / crop, corners, LK, PCA                              (base.py:354-407)
+//   rm_motion.hip         ROI mean / crop, corners, LK, PCA; the ROI means of several subjects (base.py:354-407; rm_subjects.h)
 //   rm_magnify.hip        rm_magnify, rm_magnify_bgr: frames + band-passed motion in one pass            (transforms.py:170, 181; rm_magnify.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
 // Every kernel header is included by every unit; non-template kernels are `static`, so a unit generates code only for the kernels
@@ -46,6 +46,7 @@
 #include "rm_ccl.h"
 #include "rm_flow.h"
 #include "rm_flow_clip.h"
+#include "rm_subjects.h"
 
 // sets the thread's error string (rm_last_error_string) and returns `code`
 int fail(int code, const char *fmt, ...);
@@ -349,3 +350,7 @@ int roi_launch(rm_ctx *ctx, const double *heat, int H, int W, int threshold, uin
 int roi_finish(rm_ctx *ctx, const RoiPending &pd, int32_t *xywh);
 int heatmap_to_roi_impl(rm_ctx *ctx, const double *heat, int H, int W, int threshold, int32_t *xywh, uint8_t *avg_u8, uint8_t *binary, void *stream,
                         bool have_minmax);
+// ... the ranked list of rm_heatmap_to_rois (clip_call: RM_FLAG_CONTOUR_CLIP_FRAME of the calling rm_locate_multi); a path of its own
+// that leaves the state of the single-ROI stage alone
+int heatmap_to_rois_impl(rm_ctx *ctx, const double *heat, int H, int W, int threshold, bool clip_call, int max_rois, double min_area, int32_t *xywh,
+                         double *area, int *n_out, void *stream, const char *who);

@@ -72,6 +72,24 @@ extern "C" int rm_locate(rm_ctx *ctx, const void *frames, int dtype, int T, int 
     return rc;
 }
 
+// rm_locate for several subjects: the calibration of rm_calibrate (the heatmap is the one rm_locate extracts its ROI from, bit for
+// bit; a selection that overflows the value store is summed by the dense stand-in on the stream, not by rm_locate's second look from
+// the host), then the ranked contour list.  None of rm_locate's own state -- slot 0, the refine / dense / store hints, the once-only
+// flags -- is touched.
+extern "C" int rm_locate_multi(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, double fps, double fmin, double fmax,
+                               double amp, int levels, int skip, double temporal_thr, int threshold, unsigned flags, int max_rois,
+                               double min_area, int32_t *xywh, double *area, int *n_out, void *stream)
+{
+    if (n_out) *n_out = 0;
+    if (!ctx || !xywh || !n_out || H < 1 || W < 1 || max_rois < 1 || max_rois > RM_MAX_ROIS || !(min_area >= 0.0))
+        return fail(RM_E_BADARG, "rm_locate_multi: bad argument (1 <= max_rois <= %d, min_area >= 0)", RM_MAX_ROIS);
+    double *heat = nullptr;
+    RM_TRY(ws(ctx, "heat", (size_t)H * W, &heat));
+    RM_TRY(calibrate_impl(ctx, frames, dtype, T, H, W, fps, fmin, fmax, amp, levels, skip, temporal_thr, flags, heat, nullptr, stream, nullptr));
+    return heatmap_to_rois_impl(ctx, heat, H, W, threshold, (flags & RM_FLAG_CONTOUR_CLIP_FRAME) != 0, max_rois, min_area, xywh, area, n_out, stream,
+                                "rm_locate_multi");
+}
+
 // ------------------------------------------------------------------------------------------
 // rm_locate in two calls: rm_locate_submit enqueues everything up to the packed thresholded image and returns; rm_locate_result
 // waits for it and runs the host contour stage.  Between the two the caller may submit the NEXT buffer (two tickets per context),

@@ -251,6 +251,38 @@ extern "C" int rm_roi_mean_clip(rm_ctx *ctx, const void *frames, int dtype, int 
     return RM_OK;
 }
 
+// ... for K rectangles at once (several subjects in one frame): one launch over the (frame, rectangle) pairs, one result copy, one wait
+extern "C" int rm_roi_mean_multi_clip(rm_ctx *ctx, const void *frames, int dtype, int N, int H, int W, const int32_t *rois, int K, double *out,
+                                      void *stream)
+{
+    if (!ctx || !frames || !rois || !out || N < 1 || H < 1 || W < 1 || K < 1 || K > RM_MAX_ROIS || !valid_dtype(dtype) ||
+        (long long)N * K > 0x7fffffffll)
+        return fail(RM_E_BADARG, "rm_roi_mean_multi_clip: bad argument (1 <= K <= %d)", RM_MAX_ROIS);
+    for (int k = 0; k < K; ++k)   // the whole call is refused before anything is enqueued
+        if (!roi_ok(H, W, rois[4 * k], rois[4 * k + 1], rois[4 * k + 2], rois[4 * k + 3]))
+            return fail(RM_E_BADARG, "rm_roi_mean_multi_clip: rectangle %d (%d, %d, %d, %d) does not lie inside the %d x %d frame", k, rois[4 * k],
+                        rois[4 * k + 1], rois[4 * k + 2], rois[4 * k + 3], W, H);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    double *d = nullptr;
+    int *d_rois = nullptr;
+    RM_TRY(ws(ctx, "roi_mean_multi", (size_t)N * K, &d));
+    RM_TRY(ws(ctx, "roi_mean_multi_rois", (size_t)4 * RM_MAX_ROIS, &d_rois));
+    HIP_TRY(hipMemcpyAsync(d_rois, rois, sizeof(int32_t) * 4 * (size_t)K, hipMemcpyHostToDevice, s));
+    const size_t px = (size_t)H * W;
+    const dim3 grid((unsigned)(N * K)), block(256);
+    switch (dtype) {
+    case RM_U8: hipLaunchKernelGGL((k_roi_mean_multi_clip<uint8_t>), grid, block, 0, s, (const uint8_t *)frames, px, W, (const int *)d_rois, K, d); break;
+    case RM_F16: hipLaunchKernelGGL((k_roi_mean_multi_clip<__half>), grid, block, 0, s, (const __half *)frames, px, W, (const int *)d_rois, K, d); break;
+    case RM_F32: hipLaunchKernelGGL((k_roi_mean_multi_clip<float>), grid, block, 0, s, (const float *)frames, px, W, (const int *)d_rois, K, d); break;
+    default: hipLaunchKernelGGL((k_roi_mean_multi_clip<double>), grid, block, 0, s, (const double *)frames, px, W, (const int *)d_rois, K, d); break;
+    }
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(out, d, sizeof(double) * (size_t)N * K, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));   // (the rectangles' host memory is the caller's again as well)
+    return RM_OK;
+}
+
 extern "C" int rm_pca_reduce_windows(rm_ctx *ctx, const float *motion, int n, int first, int window, double *out, void *stream)
 {
     if (!ctx || !motion || !out || n < 0 || first < 0 || first > n || window < 1) return fail(RM_E_BADARG, "rm_pca_reduce_windows: bad argument");

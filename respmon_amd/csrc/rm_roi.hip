@@ -268,6 +268,64 @@ int heatmap_to_roi_impl(rm_ctx *ctx, const double *heat, int H, int W, int thres
 }
 
 // ------------------------------------------------------------------------------------------
+// several subjects: the K largest external contours of the thresholded heatmap (rm_heatmap_to_rois, rm_locate_multi)
+// ------------------------------------------------------------------------------------------
+// A path of its own beside roi_launch / roi_finish, so that the single-ROI stage cannot tell that it ran: the packed image goes into
+// a workspace buffer of its own (k_heat_to_u8 writing every word, as it does in front of the device labelling), is copied to
+// pageable host memory behind ONE stream wait, and the borders are followed by a tracer that lives for this call
+// (rm_contour.cpp ranked_external_contours_bits).  Nothing of the pinned slots, the label_* counters, the lazy flag, the once-only
+// flags or the thread's tracer is read or written; the heatmap extrema are reduced into the state afresh, as rm_heatmap_to_roi does.
+int heatmap_to_rois_impl(rm_ctx *ctx, const double *heat, int H, int W, int threshold, bool clip_call, int max_rois, double min_area,
+                         int32_t *xywh, double *area, int *n_out, void *stream, const char *who)
+{
+    if (n_out) *n_out = 0;
+    if (!ctx || !heat || !xywh || !n_out || H < 1 || W < 1 || max_rois < 1 || max_rois > RM_MAX_ROIS || !(min_area >= 0.0))
+        return fail(RM_E_BADARG, "%s: bad argument (1 <= max_rois <= %d, min_area >= 0)", who, RM_MAX_ROIS);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    RM_TRY(ctx_stream_ok(ctx, stream, who));
+    const size_t npix = (size_t)H * W, nwords = (npix + 63) / 64;
+    unsigned long long *d_bits = nullptr;
+    RM_TRY(ws(ctx, "subjects_bits", nwords, &d_bits));
+    CollapseState *st = ctx->d_state;
+    ctx->state_fresh = false;   // the heatmap extrema are reduced into the state
+    hipLaunchKernelGGL(k_heat_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, st);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_heat_minmax<>, dim3(nblk(npix, 256, 256)), dim3(256), 0, s, heat, npix, st);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_heat_to_u8<>, dim3(nblk(npix, 256, 2048)), dim3(256), 0, s, heat, npix, W, st, threshold, (uint8_t *)nullptr, (uint8_t *)nullptr,
+                       (unsigned long long *)nullptr, (uint8_t *)nullptr, d_bits, (int *)nullptr, (CclBox *)nullptr, (unsigned int *)nullptr,
+                       (const int *)nullptr);
+    LAUNCH_CHECK();
+    std::vector<uint64_t> bits(nwords);
+    HIP_TRY(hipMemcpyAsync(bits.data(), d_bits, nwords * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    if (ctx->clip_frame || clip_call) {
+        // OpenCV <= 3.1: the 1-pixel image frame is zeroed before tracing (roi_finish does the same on its slot)
+        auto clear_bit = [&](size_t p) { bits[p >> 6] &= ~(1ull << (p & 63)); };
+        for (int y = 0; y < H; ++y) {
+            const size_t r0 = (size_t)y * W;
+            if (y == 0 || y == H - 1) { for (int x = 0; x < W; ++x) clear_bit(r0 + x); }
+            else { clear_bit(r0); clear_bit(r0 + W - 1); }
+        }
+    }
+    ContourRec recs[RM_MAX_ROIS];
+    const int n = ranked_external_contours_bits(bits.data(), H, W, max_rois, min_area, recs, nullptr);
+    for (int i = 0; i < n; ++i) {
+        xywh[4 * i] = recs[i].x; xywh[4 * i + 1] = recs[i].y; xywh[4 * i + 2] = recs[i].w; xywh[4 * i + 3] = recs[i].h;
+        if (area) area[i] = recs[i].area;
+    }
+    *n_out = n;
+    return n > 0 ? RM_OK : RM_NO_CONTOUR;
+}
+
+extern "C" int rm_heatmap_to_rois(rm_ctx *ctx, const double *heat, int H, int W, int threshold, int max_rois, double min_area,
+                                  int32_t *xywh, double *area, int *n_out, void *stream)
+{
+    return heatmap_to_rois_impl(ctx, heat, H, W, threshold, false, max_rois, min_area, xywh, area, n_out, stream, "rm_heatmap_to_rois");
+}
+
+// ------------------------------------------------------------------------------------------
 // sparse heatmap exchange (kernels: k_sparse_*)
 // ------------------------------------------------------------------------------------------
 extern "C" size_t rm_heat_sparse_packet_doubles(int cap_tiles)

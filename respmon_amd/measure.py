@@ -1,0 +1,68 @@
+"""
+The breathing signal of ONE region and what the 'measure' state does with it: the per-frame bookkeeping of reference
+base.py:473-497 and the BPM estimation of base.py:312-352.  RespiratoryMonitor (respmon_amd/base.py) is one such signal plus the
+capture / calibration state machine; respmon_amd.subjects.SubjectTracker holds one per subject of a frame.  Both run THIS code.
+
+A user of the mixin provides: fps, freq_max, filter_order, gaussian_cutoff, peak_minimum_sample_distance, measure_buffer_length,
+measure_initialization_length, save_all_data, all_data, disable_error_detection, the deques data / t / freq, the list `buffers` of
+the deques the pop-left rule applies to, and -- unless disable_error_detection is set -- detect_errors() / trigger_error().
+"""
+import numpy as np
+
+from .transforms import butter_lowpass_filter
+
+
+class BreathSignal:
+    # ------------------------------------------------------------------ BPM estimation ("next" row f2)
+    def find_peaks(self):
+        """base.py:312-338 with own restatements of peakutils.indexes / gaussian_fit (peakutils is an
+        un-pinned dependency that is not installable here: parity unpinned)."""
+        from . import peaks
+        width = self.peak_minimum_sample_distance
+        idxs = peaks.indexes(np.asarray(self.filtered_data), min_dist=width)
+        final, fits = [], []
+        t_arr = np.array(self.t)
+        f_arr = np.array(self.filtered_data)
+        for idx in idxs:
+            w = width
+            if idx - width < 0:
+                w = idx
+            if idx + w > len(self.t):
+                w = len(self.t) - idx
+            ti, di = t_arr[idx - w:idx + w], f_arr[idx - w:idx + w]
+            try:
+                params = peaks.gaussian_fit(ti, di)
+                fits.append(0.0)  # the reference's r2 is identically 0 (ssr == sst, base.py:330-332)
+                if params[2] < self.gaussian_cutoff:
+                    final.append(idx)
+            except (RuntimeError, TypeError, ValueError):
+                pass
+        return final, fits
+
+    def measure(self):
+        """base.py:340-352."""
+        self.filtered_data = np.array(butter_lowpass_filter(self.data, self.freq_max * 0.5, self.fps, self.filter_order))
+        self.peak_indices, _fits = self.find_peaks()
+        self.peak_times = np.take(self.t, self.peak_indices)
+        diffs = [a - b for b, a in zip(self.peak_times, self.peak_times[1:])]
+        if len(diffs) > 0:
+            self.freq.append(60.0 / np.mean(diffs))
+
+    def _pop_full_buffers(self):
+        for b in self.buffers:                                              # base.py:473-475
+            if len(b) >= self.measure_buffer_length:
+                b.popleft()
+
+    def _record_value(self, value):
+        """What the 'measure' state does with the value of one frame (base.py:477-497)."""
+        self.data.append(value)
+        if len(self.t) == 0:
+            self.t.append(0.)
+        else:
+            self.t.append(self.t[-1] + (1. / self.fps))
+        if self.save_all_data:
+            self.all_data.append((self.t[-1], value))
+        if len(self.data) > self.measure_initialization_length:
+            self.measure()
+            if not self.disable_error_detection and self.detect_errors():
+                self.trigger_error("error detection found poor signal")
