@@ -296,6 +296,51 @@ int rm_shard_heat(rm_ctx *ctx, const double *negmin_max_dev, double temporal_thr
 int rm_shard_finish(rm_ctx *ctx, const double *heat_sum_dev, int T, int H, int W, int threshold, double *heatmap_dev,
                     int32_t *xywh_host, void *stream);
 
+/* ---- the calibration on a SLIDING window (base.py:409-513 without the refill).  The default path filters in time before it builds
+ *      the Laplacians, so all the tail of rm_locate needs from a frame is the row rm_shard_pyramid writes for it.  An rm_window keeps
+ *      the rows of the last T frames in a ring, takes camera frames as they come, and relocates from the ring at any moment: every
+ *      frame goes through the frame-buffer kernel once in its life, a relocation costs the tail only, and after a reset of the
+ *      monitor the next ROI needs no refill.
+ *      Ring: T rows of NP doubles, NP = rm_shard_layout_flags(H, W, levels, skip, flags), allocated once by rm_window_create on the
+ *        context's device -- its own allocation, not the context's workspace, so it survives every other call on the context.  A
+ *        row holds what rm_shard_pyramid writes for one frame (G_S; the Laplacian levels S .. L-2 under RM_FLAG_FILTER_LAPLACIANS /
+ *        RM_FLAG_UNFUSED_SMALL), float64 whatever the frame dtype: successive pushes may differ in dtype.  Requires
+ *        skip_levels_at_top >= 1 like the rm_shard calls (RM_E_BADARG); T > 4096 is RM_E_UNSUPPORTED.  NP == 0 (nothing is filtered:
+ *        skip >= levels - 1): there is no ring, the heatmap is zero and the ROI stage runs on it, as in rm_shard_collapse.
+ *      rm_window_push: n >= 1 frames [n,H,W] of `dtype` (RM_BGR8: [n,H,W,3]), asynchronous on `stream`.  While the ring fills,
+ *        frame i of the call goes to row (head + count + i) mod T; once it is full a frame overwrites the oldest row and advances
+ *        head.  A call that crosses the ring's end is two launches of the frame-buffer kernel; a call with n > T reduces its last T
+ *        frames only.  The ring after a sequence of pushes depends on the frames, not on how they were grouped into calls.
+ *      rm_window_reset: count = 0, head = 0; the ring memory is kept.
+ *      rm_window_info: frames held, row of the oldest one, NP and the ring's size in bytes (any pointer may be NULL).
+ *      rm_window_calibrate / rm_window_locate / rm_window_locate_multi act on the m = min(count, T) frames held, in chronological
+ *        order, and give bit for bit what rm_calibrate / rm_locate / rm_locate_multi give on a contiguous [m,H,W] buffer of the same
+ *        frames with the window's geometry and flags: same arguments otherwise, same return codes (RM_NO_CONTOUR included).  Before
+ *        the ring is full the temporal operator is the one of T = m frames (head is 0 there); count == 0 is RM_E_BADARG.  The
+ *        window is never un-rotated or copied: the temporal kernels read frame t from row (t + head) mod T in place, in the product
+ *        order of the contiguous call, and write their output in chronological order.  The stages behind them are those of
+ *        rm_shard_collapse / rm_shard_heat with one rank; the time average and the heatmap extrema ride the sum kernel as in
+ *        rm_calibrate.  A selection that overflows the value store is summed by the dense stand-in on the stream, as in
+ *        rm_locate_multi.  rm_window_locate_multi leaves the state of the single-ROI stage alone, as rm_locate_multi does.
+ *      The three calls use the context's workspace and the plan rm_shard_collapse leaves for rm_shard_heat: they may not come
+ *        between an rm_shard_collapse and its rm_shard_heat, nor between an rm_locate_submit and its rm_locate_result on another
+ *        stream (RM_E_BUSY).  Pushes and relocations of one window belong on one stream (or on streams the caller orders): stream
+ *        order is what keeps a push off the rows a relocation still reads.  Any other call on the context may come between them.
+ *      rm_window_destroy waits for the device work that uses the ring. */
+typedef struct rm_window rm_window;
+int rm_window_create(rm_ctx *ctx, int T, int H, int W, int pyramid_levels, int skip_levels_at_top, unsigned flags, rm_window **out);
+int rm_window_destroy(rm_window *win);
+int rm_window_reset(rm_ctx *ctx, rm_window *win);
+int rm_window_push(rm_ctx *ctx, rm_window *win, const void *frames_dev, int dtype, int n, void *stream);
+int rm_window_info(const rm_window *win, int *count, int *head, size_t *np, size_t *ring_bytes);
+int rm_window_calibrate(rm_ctx *ctx, rm_window *win, double fps, double freq_min, double freq_max, double amplification,
+                        double temporal_threshold, double *heatmap_dev, void *stream);
+int rm_window_locate(rm_ctx *ctx, rm_window *win, double fps, double freq_min, double freq_max, double amplification,
+                     double temporal_threshold, int threshold, int32_t *xywh_host, void *stream);
+int rm_window_locate_multi(rm_ctx *ctx, rm_window *win, double fps, double freq_min, double freq_max, double amplification,
+                           double temporal_threshold, int threshold, int max_rois, double min_area, int32_t *xywh_host,
+                           double *area_host, int *n_host, void *stream);
+
 /* ---- base.py:355-358 + 471: extract_motion('average') = np.average(frame[y:y+h, x:x+w]) -- */
 int rm_roi_mean(rm_ctx *ctx, const void *frame_dev, int dtype, int H, int W, int x, int y, int w, int h,
                 double *out_host, void *stream);

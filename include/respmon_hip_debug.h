@@ -42,6 +42,10 @@ const char *rm_debug_kernel_source_stamp(void);
  * [unique frame][tile] bounds of the selection; "cS": the collapsed band-passed level) -- tests check the bounds themselves with it */
 int rm_debug_workspace(rm_ctx *ctx, const char *name, void *out_host, size_t bytes, void *stream);
 
+/* the ring of an rm_window as it lies in memory: rows [row0, row0 + nrows) of NP doubles each (row r holds frame j of the stream with
+ * j mod T == r), copied to out_host after the work queued on `stream` */
+int rm_debug_window_rows(rm_ctx *ctx, const rm_window *win, int row0, int nrows, double *out_host, void *stream);
+
 /* host timeline of the last rm_locate on this context, microseconds on the steady clock relative to the entry of that call:
  * out_host[0] = entry of the call minus the return of the PREVIOUS rm_locate (what the caller spent between two calls),
  * [1] = first kernel launch issued, [2] = every launch issued, [3] = device work seen complete, [4] = host contour stage done

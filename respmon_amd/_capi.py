@@ -85,6 +85,15 @@ SIGNATURES = {
     "rm_shard_collapse": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _d, _u, _vp, _vp]),
     "rm_shard_heat": (_i, [_vp, _vp, _d, _vp, _vp]),
     "rm_shard_finish": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "rm_window_create": (_i, [_vp, _i, _i, _i, _i, _i, _u, _c.POINTER(_vp)]),
+    "rm_window_destroy": (_i, [_vp]),
+    "rm_window_reset": (_i, [_vp, _vp]),
+    "rm_window_push": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "rm_window_info": (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_sz), _c.POINTER(_sz)]),
+    "rm_window_calibrate": (_i, [_vp, _vp, _d, _d, _d, _d, _d, _vp, _vp]),
+    "rm_window_locate": (_i, [_vp, _vp, _d, _d, _d, _d, _d, _i, _vp, _vp]),
+    "rm_window_locate_multi": (_i, [_vp, _vp, _d, _d, _d, _d, _d, _i, _i, _d, _vp, _vp, _c.POINTER(_i), _vp]),
+    "rm_debug_window_rows": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "rm_roi_mean": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_roi_to_uint8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_good_features_to_track": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp]),

@@ -336,14 +336,26 @@ class RespiratoryMonitor(BreathSignal):
 
     def __init__(self, capture_target=0, save_calibration_image=False, visualize='pyqtgraph', fig_size=None,
                  fps_limit=10, error_reset_delay=10.0, save_all_data=True,
-                 motion_extraction_method='average', buffer_dtype='float64', run_on_init=True, backend=None):
+                 motion_extraction_method='average', buffer_dtype='float64', run_on_init=True, backend=None, relocate_every=0):
         """Arguments as reference base.py:24-34, plus (not in the reference):
         buffer_dtype -- element type of the calibration buffer in HBM: 'float64' (the reference's, base.py:119), 'float32',
             'float16', 'uint8' (the gray frame as ingested; uint8_to_float happens where the buffer is read) or 'bgr8' (a
             [T,H,W,3] uint8 buffer of the frames AS CAPTURED: cvtColor + uint8_to_float happen where the buffer is read; next_frame()
             keeps the device copy of the captured frame for step(), a frame from anywhere else is stored as its gray value in
             three planes -- the same calibration either way);
-        run_on_init -- False: construct without entering run(); backend -- a stand-in for the device backend (tests)."""
+        run_on_init -- False: construct without entering run(); backend -- a stand-in for the device backend (tests);
+        relocate_every -- 0 (default): the reference's one-shot calibration buffer, nothing else.  n > 0: every frame that is stored or
+            measured also goes into a sliding window on the device (respmon_amd/window.py SlidingCalibration: a ring of per-frame
+            pyramid rows, calibration_buffer_target_length frames long); once the first locate() has put the monitor into 'measure',
+            the ROI is taken again from the ring every n measured frames (kept when the ring shows no contour), and after a reset()
+            the ring is still there: the next ROI comes from it with the next frame instead of after a refill of the buffer.
+            step_clip() cuts its clips where the ROI is refreshed, so clips and single frames give the same ROIs.  In 'flow' mode
+            a refresh that changes the ROI starts the tracking again on the new rectangle (new corners, motion_data emptied), as
+            a reset() does; the value of that frame and of the next is 0.0, as on the first two frames of any tracking session.
+            Two things to know: while a full ring shows no contour, every calibration frame tries the ring again (one
+            host-synchronous call per frame) until an ROI turns up, alongside the refill of the buffer; and no frame is pushed in
+            the 'error' state, so after such a pause the ring holds frames from both sides of a gap of error_reset_delay seconds,
+            which the band-pass reads as consecutive until T new frames have replaced them."""
         # argument contract of reference base.py:24-34
         assert isinstance(fps_limit, (int, float)) and fps_limit > 0, "fps_limit must be a positive int or float"
         assert isinstance(save_calibration_image, bool), "save_calibration_image must be bool"
@@ -355,6 +367,7 @@ class RespiratoryMonitor(BreathSignal):
         assert isinstance(save_all_data, bool), "save_all_data should be bool"
         assert motion_extraction_method in ("average", "flow"), "motion_extraction_method must be 'average' or 'flow'"
         assert buffer_dtype in ("float64", "float32", "float16", "uint8", "bgr8")
+        assert isinstance(relocate_every, int) and relocate_every >= 0, "relocate_every must be a non-negative int"
 
         self.benchmarker = Benchmarker()
         self.error_reset_delay = error_reset_delay
@@ -366,6 +379,10 @@ class RespiratoryMonitor(BreathSignal):
         self.motion_extraction_method = motion_extraction_method
         self.buffer_dtype = buffer_dtype
         self._backend = backend if backend is not None else _Backend()
+        self.relocate_every = relocate_every
+        self._window = None              # SlidingCalibration, made with the first frame it is given (relocate_every > 0)
+        self._window_stage = None        # staging buffer of the calibration buffer's dtype for the frames of 'measure'
+        self._since_relocate = 0
 
         self.cap = self._open_capture(capture_target)                       # base.py:48
         self.fps = int(self.cap.get(self.CAP_PROP_FPS))                     # base.py:49
@@ -762,6 +779,8 @@ class RespiratoryMonitor(BreathSignal):
     def _measure_clip(self, frames):
         x, y, w, h = self.x, self.y, self.w, self.h
         be = self._backend
+        if self.relocate_every > 0:
+            frames = frames[:self.relocate_every - self._since_relocate]    # a clip ends where the ROI is taken again
         n = len(frames)
         if self.motion_extraction_method == "average":
             means = be.roi_mean_clip(frames, x, y, w, h)
@@ -789,7 +808,10 @@ class RespiratoryMonitor(BreathSignal):
             self._record_value(value_of(i))
             self.benchmarker.tick_end('Measurement Loop')
             if self.state != 'measure':
-                return i + 1
+                n = i + 1
+                break
+        if self.relocate_every > 0:
+            self._window_measured(frames[:n])
         return n
 
     def _flow_clip_values(self, be, frames, x, y, w, h):
@@ -839,6 +861,11 @@ class RespiratoryMonitor(BreathSignal):
                 else:
                     self._backend.store_frame(self.calibration_buffer, self.calibration_buffer_idx, frame)
                 self.calibration_buffer_idx += 1
+                if self.relocate_every > 0:
+                    was_full = self._window is not None and self._window.count >= self._window.T
+                    self._window_push(self.calibration_buffer[self.calibration_buffer_idx - 1:self.calibration_buffer_idx])
+                    if was_full:   # a reset() kept the ring: the ROI comes from it now, not after a refill
+                        self._enter_measure(self._locate_window())
             else:
                 logging.info("Finished capturing calibration frames. Beginning calibration...")
                 self.detect_fps()
@@ -851,6 +878,7 @@ class RespiratoryMonitor(BreathSignal):
                     self.calibration_buffer_idx = 0
                     return
                 self.x, self.y, self.w, self.h = reduce_bounding_box(*location, self.maximum_bounding_box_area)
+                self._since_relocate = 0
                 logging.info("Finished calibration.")
                 logging.info("Beginning measuring...")
                 self.state = 'measure'
@@ -860,11 +888,65 @@ class RespiratoryMonitor(BreathSignal):
             self._pop_full_buffers()
             self._record_value(self.extract_motion())
             self.benchmarker.tick_end('Measurement Loop')
+            if self.relocate_every > 0:
+                self._window_measured([frame])
         elif self.state == 'error':
             if time.time() - self.reset_start_time >= self.error_reset_delay:
                 logging.info('Benchmark Report...\r\n' + self.benchmarker.get_report())
                 self.reset()
                 self.state = 'calibration'
+
+    # ------------------------------------------------------------------ sliding window (relocate_every > 0)
+    def _window_push(self, frames):
+        if self._window is None:
+            assert isinstance(self._backend, _Backend), "relocate_every > 0 needs the device backend"
+            from .window import SlidingCalibration
+            self._window = SlidingCalibration(self.calibration_buffer_target_length, self.height, self.width, 9, 4)
+        self._window.push(frames, bgr=self.buffer_dtype == "bgr8")
+
+    def _window_measured(self, frames):
+        """The frames just measured go into the ring -- through a staging buffer of the calibration buffer's dtype, so the ring sees
+        what store_frame stores -- and after relocate_every of them the ROI is taken again."""
+        n = len(frames)
+        stage = self._window_stage
+        if stage is None or len(stage) < n:
+            stage = self._window_stage = self.calibration_buffer.new_empty((n,) + tuple(self.calibration_buffer.shape[1:]))
+        for i in range(n):
+            if self.buffer_dtype == "bgr8":
+                bgr = self._frame_bgr if frames[i] is getattr(self, "_frame_u8", None) else None
+                self._backend.store_frame(stage, i, frames[i], bgr=bgr)
+            else:
+                self._backend.store_frame(stage, i, frames[i])
+        self._window_push(stage[:n])
+        self._since_relocate += n
+        if self._since_relocate >= self.relocate_every:
+            self._since_relocate = 0
+            self._set_roi(self._locate_window())
+
+    def _set_roi(self, location):
+        """the ROI of a refresh; None (no contour in the ring) keeps the one held"""
+        if location is None:
+            return
+        roi = tuple(reduce_bounding_box(*location, self.maximum_bounding_box_area))
+        if roi != (self.x, self.y, self.w, self.h) and self.motion_extraction_method == "flow":
+            # the crop, its corners and the displacements gathered so far belong to the old rectangle: tracking begins again
+            # (rm_flow_begin, or goodFeaturesToTrack on the four-call path) with the next frame
+            self.previous_cropped_image = None
+            self.motion_key_points = None
+            self.motion_data.clear()
+        self.x, self.y, self.w, self.h = roi
+
+    def _locate_window(self):
+        """_locate_buffer on the frames the ring holds"""
+        return self._window.locate(self.fps, self.freq_min, self.freq_max, 500, self.temporal_threshold, int(np.round(self.threshold * 255)))
+
+    def _enter_measure(self, location):
+        if location is None:
+            return
+        self.peak_minimum_sample_distance = int(np.floor(self.fps / self.freq_max))
+        self.x, self.y, self.w, self.h = reduce_bounding_box(*location, self.maximum_bounding_box_area)
+        self._since_relocate = 0
+        self.state = 'measure'
 
     def _locate_buffer(self):
         """the locate() call of run(), base.py:444-448: threshold = int(round(0.08*255)) = 20; pyramid_levels=9,

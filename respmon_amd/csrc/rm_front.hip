@@ -126,7 +126,7 @@ int front_pyramid(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int 
 }
 
 int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, double fps, double fmin, double fmax, double amp,
-                        SmallLevels &out, hipStream_t s)
+                        SmallLevels &out, hipStream_t s, int head)
 {
     const std::vector<int> &h = pg.h, &w = pg.w;
     const int L = pg.L, S = pg.S;
@@ -145,7 +145,7 @@ int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, doubl
     if (pg.filter_first) {
         // X = B(G_S) for the unique frames (its workgroup 0 resets the reduction state), then ONE per-frame kernel: Gaussian levels
         // of X, Laplacians, collapse to C_S, tile bounds and lattice samples
-        RM_TRY(launch_temporal(ctx, lap, T, NP, op, amp, bp, s, ctx->d_state));
+        RM_TRY(launch_temporal(ctx, lap, T, NP, op, amp, bp, s, ctx->d_state, false, head));
         ChainGeom cg;
         SmallLevels probe; probe.h = pg.h; probe.w = pg.w; probe.S = S;
         RM_TRY(make_geom(probe, cg));
@@ -178,7 +178,7 @@ int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, doubl
         // X_S = B(G_S); X_{L-1} = pyrDown^(L-1-S)(X_S); U_{L-1} = X_{L-1}, U_l = pyrUp(U_{l+1}); C_S = X_S - pyrUp(U_{S+1})
         // (rm_kernels.h k_small_filter_first: the telescoped collapse, here with one launch per step): only the COARSEST level of
         // the filtered pyramid is needed, so the way down is the fused pyrDown chain (rm_down_chain.h) on the float64 level X_S
-        RM_TRY(launch_temporal(ctx, lap, T, NP, op, amp, bp, s, ctx->d_state));   // (its workgroup 0 resets the reduction state: no k_state_init launch)
+        RM_TRY(launch_temporal(ctx, lap, T, NP, op, amp, bp, s, ctx->d_state, false, head));   // (its workgroup 0 resets the reduction state: no k_state_init launch)
         out.state_ready = true;
         std::vector<double *> x(L, nullptr);
         x[S] = bp;
@@ -216,7 +216,7 @@ int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, doubl
         return RM_OK;
     }
     // temporal band-pass of every level at once (transforms.py:162,169)
-    RM_TRY(launch_temporal(ctx, lap, T, NP, op, amp, bp, s));
+    RM_TRY(launch_temporal(ctx, lap, T, NP, op, amp, bp, s, nullptr, false, head));
     // collapse of the band-passed levels L-2 .. S (pyramid.py:51-57; the coarsest level is zeros: 0 + x == x);
     // the result is a contiguous [Th,h_S,w_S] array for the full-resolution passes
     const double *c = bp + pg.off[L - 2];

@@ -13,6 +13,7 @@
 //   rm_locate.hip         rm_locate, rm_locate_submit / rm_locate_result                 (base.py:547-601)
 //   rm_comm.hip           RCCL behind the C-ABI                                          
 //   rm_motion.hip         ROI mean / crop, corners, LK, PCA; the ROI means of several subjects (base.py:354-407; rm_subjects.h)
+//   rm_window.hip         rm_window_*: a ring of per-frame pyramid rows, relocated in place          (base.py:409-513 without the refill)
 //   rm_magnify.hip        rm_magnify, rm_magnify_bgr: frames + band-passed motion in one pass            (transforms.py:170, 181; rm_magnify.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
 // Every kernel header is included by every unit; non-template kernels are `static`, so a unit generates code only for the kernels
@@ -296,7 +297,7 @@ void level_sizes(int H, int W, int levels, std::vector<int> &h, std::vector<int>
 struct TemporalOp { const double *R = nullptr, *C = nullptr, *Rf = nullptr, *Cf = nullptr; int nk = 0, tiles = 0; };  // nk: merged rows; Rf / Cf: fragment-major copies for k_temporal_sym<tiles>
 int get_operator(rm_ctx *ctx, int T, double fps, double fmin, double fmax, TemporalOp *op, hipStream_t s);
 int launch_temporal(rm_ctx *ctx, const double *x, int T, size_t NP, const TemporalOp &op, double amp, double *out, hipStream_t s,
-                    rm::CollapseState *st_init = nullptr, bool full = false);
+                    rm::CollapseState *st_init = nullptr, bool full = false, int head = 0);   // head > 0: x is a ring of T rows, oldest frame in row `head`
 
 // ---- rm_down.hip: frames[T,H,W] -> G_S[T,h_S,w_S] in one launch
 int launch_down_chain(rm_ctx *ctx, const void *frames, int dtype, int T, const std::vector<int> &h, const std::vector<int> &w, int S,
@@ -329,7 +330,7 @@ struct PyrGeom {
 void pyr_geom(int H, int W, int levels, int skip, unsigned flags, PyrGeom &pg);
 int front_pyramid(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, const PyrGeom &pg, unsigned flags, double *lap, hipStream_t s);
 int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, double fps, double fmin, double fmax, double amp, SmallLevels &out,
-                 hipStream_t s);
+                 hipStream_t s, int head = 0);   // head > 0: lap is a ring of T rows (launch_temporal); nothing behind the temporal filter knows
 int front_half(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, double fps, double fmin, double fmax, double amp, int levels,
                int skip, unsigned flags, SmallLevels &out, hipStream_t s);
 int make_geom(const SmallLevels &sl, rm::ChainGeom &g);

@@ -377,8 +377,20 @@ constexpr int TF_KC = 4, TF_SC = 8, TF_U = 16;
 // scalar-load and global-load latency, the two-stage form has 8-20 waves per CU to hide them).
 __device__ void state_init_lane(struct CollapseState *st, int i);   // defined with the state, below
 
+// The input of the temporal kernels may be a RING of T rows (rm_window.hip): frame t of the chronological window is row t + head,
+// minus T when that reaches T (0 <= head < T).  RING is a compile-time variant: with RING == 0 `head` is never read and the kernels are
+// the ones every call on a contiguous [T, NP] buffer has always run.  The row index is integer arithmetic on values known before any
+// load is issued, so the up-front batches of x loads stay independent of each other; the outputs are in chronological order.
+template <int RING> __device__ __forceinline__ int ring_row(int t, int head, int T)
+{
+    if (RING) { const int r = t + head; return r >= T ? r - T : r; }
+    return t;
+}
+
 // st_init (nullable): workgroup (0, 0) also resets the reduction state of the collapse passes that follow on the stream
-RM_KERNEL __launch_bounds__(64) void k_temporal_fwd(const double *x, int T, size_t NP, const double *R, int nk, double *y, struct CollapseState *st_init)
+template <int RING = 0>
+__global__ __launch_bounds__(64) void k_temporal_fwd(const double *x, int T, size_t NP, const double *R, int nk, double *y, struct CollapseState *st_init,
+                                                     int head)
 {
     HIP_DYNAMIC_SHARED(double, s_r)  // [T][TF_KC]
     if (st_init && blockIdx.x == 0 && blockIdx.y == 0) state_init_lane(st_init, (int)threadIdx.x);
@@ -396,7 +408,7 @@ RM_KERNEL __launch_bounds__(64) void k_temporal_fwd(const double *x, int T, size
     for (int t0 = 0; t0 < T; t0 += TF_U) {
         double v[TF_U];
 #pragma unroll
-        for (int u = 0; u < TF_U; ++u) v[u] = (t0 + u < T) ? x[(size_t)(t0 + u) * NP + p] : 0.0;
+        for (int u = 0; u < TF_U; ++u) v[u] = (t0 + u < T) ? x[(size_t)ring_row<RING>(t0 + u, head, T) * NP + p] : 0.0;
 #pragma unroll
         for (int u = 0; u < TF_U; ++u) {
             if (t0 + u < T) {
@@ -476,10 +488,10 @@ constexpr int TM_MAX_HALF = 3;     // up to 48 merged rows per symmetry class (n
 typedef RM_VEC(double, 4) v4f64;
 
 // mirror_n > 0: also store output frame s as frame mirror_n - s (the full [n, NP] array of the module-level filter call)
-template <int NH>
+template <int NH, int RING = 0>
 __global__ __launch_bounds__(64 * TM_W, NH == 1 ? 3 : 2) void k_temporal_sym(const double *__restrict__ x, int T, size_t NP, const double *__restrict__ Rf,
                                                              const double *__restrict__ Cf, double amp, double *__restrict__ out, int mirror_n,
-                                                             struct CollapseState *st_init)
+                                                             struct CollapseState *st_init, int head)
 {
     RM_TRACE_SCOPE(2);
     if (st_init && blockIdx.x == 0 && threadIdx.x < 64) state_init_lane(st_init, (int)threadIdx.x);
@@ -507,8 +519,8 @@ __global__ __launch_bounds__(64 * TM_W, NH == 1 ? 3 : 2) void k_temporal_sym(con
             const int ks = kc + i * TM_W;
             if (ks < nks) {   // (wave-uniform)
                 const int t = 4 * ks + hi, tc = t < Th ? t : Th - 1, tp = tc == 0 ? 0 : T - tc;
-                xa[i] = x[(size_t)tc * NP + pc];
-                xb[i] = x[(size_t)tp * NP + pc];
+                xa[i] = x[(size_t)ring_row<RING>(tc, head, T) * NP + pc];
+                xb[i] = x[(size_t)ring_row<RING>(tp, head, T) * NP + pc];
             }
         }
 #pragma unroll
@@ -606,10 +618,10 @@ __global__ __launch_bounds__(64 * TM_W, NH == 1 ? 3 : 2) void k_temporal_sym(con
 // The products into each accumulator happen in the same order as in k_temporal_sym?  No: there the partial sums of the four K-phases
 // are added in wave order -- here K runs straight through.  The two kernels agree to rounding (~1e-16), and a given (T, level size)
 // always takes the same one.
-template <int NH>
+template <int NH, int RING = 0>
 __global__ __launch_bounds__(256, 2) void k_temporal_sym_px(const double *__restrict__ x, int T, size_t NP, const double *__restrict__ Rf,
                                                             const double *__restrict__ Cf, double amp, double *__restrict__ out, int mirror_n,
-                                                            struct CollapseState *st_init)
+                                                            struct CollapseState *st_init, int head)
 {
     if (st_init && blockIdx.x == 0 && threadIdx.x < 64) state_init_lane(st_init, (int)threadIdx.x);
     constexpr int NT = 2 * NH;
@@ -633,8 +645,8 @@ __global__ __launch_bounds__(256, 2) void k_temporal_sym_px(const double *__rest
         for (int i = 0; i < TP_XC; ++i) {
             const int ks = k0 + i;
             const int t = 4 * (ks < nks ? ks : nks - 1) + hi, tc = t < Th ? t : Th - 1, tp = tc == 0 ? 0 : T - tc;
-            xa[buf][i] = x[(size_t)tc * NP + pc];
-            xb[buf][i] = x[(size_t)tp * NP + pc];
+            xa[buf][i] = x[(size_t)ring_row<RING>(tc, head, T) * NP + pc];
+            xb[buf][i] = x[(size_t)ring_row<RING>(tp, head, T) * NP + pc];
         }
     };
     // this thread's share of a fragment chunk: global -> registers (in flight while the previous chunk is multiplied) -> LDS

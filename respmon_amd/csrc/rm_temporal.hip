@@ -214,8 +214,11 @@ int get_operator(rm_ctx *ctx, int T, double fps, double fmin, double fmax, Tempo
 
 // out[Th, NP] = amp * Cz (Rz x), x[T, NP]: the Th = T / 2 + 1 unique frames of the band-passed signal (transforms.py:86-99);
 // full = true: out is [T, NP] and the mirrored frames are stored as well
-int launch_temporal(rm_ctx *ctx, const double *x, int T, size_t NP, const TemporalOp &op, double amp, double *out, hipStream_t s,
-                           CollapseState *st_init, bool full)
+// RING = 1 (head in 1 .. T-1): x is a ring of T rows whose oldest frame is row `head` (rm_window.hip); whichever form is due reads
+// frame t from row (t + head) mod T.  RING = 0 (head == 0): x is contiguous, the instantiations every other call runs.
+template <int RING>
+static int launch_temporal_forms(rm_ctx *ctx, const double *x, int T, size_t NP, const TemporalOp &op, double amp, double *out, hipStream_t s,
+                                 CollapseState *st_init, bool full, int head)
 {
     const int Th = sym_frames(T);
     if (op.nk == 0) {  // nothing survives the mask
@@ -230,17 +233,17 @@ int launch_temporal(rm_ctx *ctx, const double *x, int T, size_t NP, const Tempor
     const bool wide = ctx->dbg.temporal_wide >= 0 ? ctx->dbg.temporal_wide != 0 : NP >= (size_t)64 * 4 * cus_t;
     if (op.Rf && !ctx->dbg.temporal_valu && wide) {
         const dim3 grid((unsigned)((NP + 63) / 64)), block(256);
-        if (op.tiles == 1) hipLaunchKernelGGL((k_temporal_sym_px<1>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init);
-        else if (op.tiles == 2) hipLaunchKernelGGL((k_temporal_sym_px<2>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init);
-        else hipLaunchKernelGGL((k_temporal_sym_px<3>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init);
+        if (op.tiles == 1) hipLaunchKernelGGL((k_temporal_sym_px<1, RING>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init, head);
+        else if (op.tiles == 2) hipLaunchKernelGGL((k_temporal_sym_px<2, RING>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init, head);
+        else hipLaunchKernelGGL((k_temporal_sym_px<3, RING>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init, head);
         LAUNCH_CHECK();
         return RM_OK;
     }
     if (op.Rf && !ctx->dbg.temporal_valu) {
         const dim3 grid((unsigned)((NP + 15) / 16)), block(64 * TM_W);
-        if (op.tiles == 1) hipLaunchKernelGGL((k_temporal_sym<1>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init);
-        else if (op.tiles == 2) hipLaunchKernelGGL((k_temporal_sym<2>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init);
-        else hipLaunchKernelGGL((k_temporal_sym<3>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init);
+        if (op.tiles == 1) hipLaunchKernelGGL((k_temporal_sym<1, RING>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init, head);
+        else if (op.tiles == 2) hipLaunchKernelGGL((k_temporal_sym<2, RING>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init, head);
+        else hipLaunchKernelGGL((k_temporal_sym<3, RING>), grid, block, 0, s, x, T, NP, op.Rf, op.Cf, amp, out, mirror_n, st_init, head);
         LAUNCH_CHECK();
         return RM_OK;
     }
@@ -249,11 +252,19 @@ int launch_temporal(rm_ctx *ctx, const double *x, int T, size_t NP, const Tempor
     double *y = nullptr;
     RM_TRY(ws(ctx, "temporal_y", (size_t)op.nk * NP, &y));
     dim3 g1((unsigned)((NP + 63) / 64), (op.nk + TF_KC - 1) / TF_KC), g2((unsigned)((NP + 63) / 64), (Th + TF_SC - 1) / TF_SC);
-    hipLaunchKernelGGL(k_temporal_fwd<>, g1, dim3(64), sh1, s, x, T, NP, op.R, op.nk, y, st_init);
+    hipLaunchKernelGGL(k_temporal_fwd<RING>, g1, dim3(64), sh1, s, x, T, NP, op.R, op.nk, y, st_init, head);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_temporal_inv<>, g2, dim3(64), sh2, s, y, op.nk, NP, op.C, Th, amp, out, mirror_n);
     LAUNCH_CHECK();
     return RM_OK;
+}
+
+int launch_temporal(rm_ctx *ctx, const double *x, int T, size_t NP, const TemporalOp &op, double amp, double *out, hipStream_t s,
+                    CollapseState *st_init, bool full, int head)
+{
+    if (head < 0 || head >= T) return fail(RM_E_BADARG, "temporal filter: ring head %d outside [0, %d)", head, T);
+    if (head > 0) return launch_temporal_forms<1>(ctx, x, T, NP, op, amp, out, s, st_init, full, head);
+    return launch_temporal_forms<0>(ctx, x, T, NP, op, amp, out, s, st_init, full, 0);   // (a ring whose oldest frame is row 0 is a contiguous buffer)
 }
 
 extern "C" int rm_temporal_bandpass_filter_fft(rm_ctx *ctx, const double *data, int T, size_t npix, double fps, double fmin,
