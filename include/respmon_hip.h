@@ -418,6 +418,32 @@ int rm_pca_reduce_windows(rm_ctx *ctx, const float *motion_host, int n, int firs
  *        K == 1 equals rm_roi_mean_clip. */
 int rm_roi_mean_multi_clip(rm_ctx *ctx, const void *frames_dev, int dtype, int N, int H, int W,
                            const int32_t *rois_host /* [K][4] x,y,w,h */, int K, double *out_host /* [N][K] */, void *stream);
+/*      rm_flow_multi_clip: K subjects by optical flow in one call = exactly K rm_flow_clip calls, subject k on states_host[k] with
+ *        rectangle rois_host[k], bit for bit: mean_xy_host[i][k], n_good_host[i][k] for every frame i, and the state every
+ *        rm_flow_state is left in (the last crop with its pyramid, the survivors packed in point order, the point count), so
+ *        rm_flow_step, rm_flow_clip, rm_flow_multi_clip and rm_flow_points may be mixed freely on a state and a clip may be split
+ *        anywhere.  A subject whose state has no points left only advances its previous image to the clip's last frame; its outputs
+ *        are zeros.  The subjects share every launch: the front kernels run over (pixel block, image, subject), the tracker is one
+ *        wavefront per (subject, point), the finish one workgroup per (frame, subject); the launches of a chunk grow with the level
+ *        count only, the call makes one table upload, one result copy and one stream wait.  The chunk workspace (256 MiB at most,
+ *        summed over the subjects) belongs to the context.
+ *        Refusal is all or nothing -- nothing is enqueued, no state is touched, no output is written; the error text names the
+ *        first offending subject.  RM_E_BADARG: K outside 1..RM_MAX_ROIS, N < 1, NULL pointers (a NULL entry of states_host
+ *        included), a dtype that is no frame dtype, win_w or win_h < 3, max_level < 0, N * K beyond int, a rectangle outside the
+ *        frame, a state that is not begun, was begun for another ROI size or belongs to another device, the same state twice.
+ *        RM_E_UNSUPPORTED where rm_flow_clip returns it for a subject that still has points.  K == 1 equals rm_flow_clip.
+ *      rm_pca_reduce_windows_multi: K motion lists in one call.  motion_host holds the rows of all lists; seg_host[k] = {first row
+ *        of list k, its number of rows n_k, first_k}; out_host takes, list after list, the n_k - first_k values
+ *        rm_pca_reduce_windows(rows of k, n_k, first_k, window) returns, bit for bit.  One upload, one launch, one download, one
+ *        wait.  A list with first_k == n_k contributes nothing.  RM_E_BADARG: K outside 1..RM_MAX_ROIS, window < 1, a negative
+ *        entry, first_k > n_k, lists that overlap.  K == 1 equals rm_pca_reduce_windows. */
+int rm_flow_multi_clip(rm_ctx *ctx, rm_flow_state *const *states_host /* [K] */, const void *frames_dev, int dtype,
+                       int N, int H, int W, const int32_t *rois_host /* [K][4] x,y,w,h */, int K,
+                       int win_w, int win_h, int max_level, int max_count, double epsilon,
+                       float *mean_xy_host /* [N][K][2] */, int32_t *n_good_host /* [N][K] */, void *stream);
+int rm_pca_reduce_windows_multi(rm_ctx *ctx, const float *motion_host /* rows of all lists, [.][2] */,
+                                const int32_t *seg_host /* [K][3]: first row, n rows, `first` */, int K, int window,
+                                double *out_host /* sum_k (n_k - first_k) values, list after list */, void *stream);
 
 /* ---- multi-GPU steps with RCCL behind the C-ABI (the call site they replace is base.py:444, run once per GPU).
  *      One process per GPU, one context per process.  librccl is opened at run time (dlopen), so single-GPU users never need it.

@@ -109,6 +109,8 @@ SIGNATURES = {
     "rm_roi_mean_multi_clip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "rm_flow_clip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
     "rm_pca_reduce_windows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "rm_flow_multi_clip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
+    "rm_pca_reduce_windows_multi": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "rm_bgr_to_gray": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "rm_comm_unique_id": (_i, [_vp]),
     "rm_comm_init": (_i, [_vp, _i, _i, _vp]),

@@ -329,6 +329,46 @@ class _Backend:
                                                              ctypes.c_void_p(out.ctypes.data), device.stream_ptr()), "rm_pca_reduce_windows")
         return out
 
+    # -- several subjects per clip: K flow_clip calls, K pca_reduce_windows calls as one call each ------------------------------
+    def flow_multi_clip(self, states, frames, rois, winSize, maxLevel, criteria):
+        """(mean [N,K,2] float32, n_good [N,K] int32): flow_clip of subject k on states[k] with rectangle rois[k], in one call."""
+        import ctypes
+        frames = frames.contiguous()
+        N, H, W = frames.shape
+        r = np.ascontiguousarray(rois, dtype=np.int32).reshape(-1, 4)
+        K = len(r)
+        assert len(states) == K, "one flow state per rectangle"
+        handles = (ctypes.c_void_p * K)(*[st.handle for st in states])
+        ctype, max_count, eps = criteria
+        if not (ctype & 1):
+            max_count = 30
+        if not (ctype & 2):
+            eps = 0.01
+        mean = np.empty((N, K, 2), dtype=np.float32)
+        ng = np.empty((N, K), dtype=np.int32)
+        _capi.check(self.lib, self.lib.rm_flow_multi_clip(device.ctx(), handles, device.ptr(frames), device.dtype_code(frames), N, H, W,
+                                                          ctypes.c_void_p(r.ctypes.data), K, int(winSize[0]), int(winSize[1]), int(maxLevel),
+                                                          int(max_count), float(eps), ctypes.c_void_p(mean.ctypes.data),
+                                                          ctypes.c_void_p(ng.ctypes.data), device.stream_ptr()), "rm_flow_multi_clip")
+        return mean, ng
+
+    def pca_reduce_windows_multi(self, rows_list, firsts, window):
+        """[pca_reduce_windows(rows_list[k], firsts[k], window) for every k], in one call."""
+        import ctypes
+        rows = [np.ascontiguousarray(m, dtype=np.float32).reshape(-1, 2) for m in rows_list]
+        seg = np.empty((len(rows), 3), dtype=np.int32)
+        at = 0
+        for k, m in enumerate(rows):
+            seg[k] = (at, len(m), int(firsts[k]))
+            at += len(m)
+        allrows = np.concatenate(rows) if rows else np.empty((0, 2), np.float32)
+        counts = [int(n - f) for _, n, f in seg]
+        out = np.empty(max(sum(counts), 1), dtype=np.float64)
+        _capi.check(self.lib, self.lib.rm_pca_reduce_windows_multi(device.ctx(), ctypes.c_void_p(allrows.ctypes.data), ctypes.c_void_p(seg.ctypes.data),
+                                                                   len(rows), int(window), ctypes.c_void_p(out.ctypes.data), device.stream_ptr()),
+                    "rm_pca_reduce_windows_multi")
+        return [a.copy() for a in np.split(out[:sum(counts)], np.cumsum(counts)[:-1])]
+
 
 class RespiratoryMonitor(BreathSignal):
     CAP_PROP_FRAME_WIDTH, CAP_PROP_FRAME_HEIGHT, CAP_PROP_FPS = 3, 4, 5
@@ -825,28 +865,9 @@ class RespiratoryMonitor(BreathSignal):
         if not had_points:
             return lambda i: np.nan
         self._points_stale = True
-        # rows this clip appends to motion_data: the frames in front of the one that loses the last point.  The deque holds at most
-        # measure_buffer_length rows (popleft before every frame), so frame i's PCA runs over that many rows ending in its own.
-        k = 0
-        while k < len(n_good) and n_good[k] > 0:
-            k += 1
-        first = len(self.motion_data)
-        pca = []
-        if k:
-            rows = np.array(list(self.motion_data) + [[mean[i][0], mean[i][1]] for i in range(k)], dtype=np.float32)
-            pca = be.pca_reduce_windows(rows, first, self.measure_buffer_length)
-
-        def value(i):
-            if self._flow_n == 0:
-                return np.nan
-            self._flow_n = int(n_good[i])
-            if self._flow_n == 0:
-                return np.nan                                               # base.py:385-386 (the object np.nan: detect_errors tests identity)
-            self.motion_data.append([mean[i][0], mean[i][1]])               # base.py:389
-            if len(self.motion_data) >= 2:
-                return float(pca[i])                                        # base.py:396-405
-            return 0.0
-        return value
+        rows, first = self._flow_clip_rows(mean, n_good)
+        pca = be.pca_reduce_windows(rows, first, self.measure_buffer_length) if len(rows) > first else []
+        return self._flow_clip_replay(mean, n_good, pca)
 
     def step(self, frame):
         """One iteration of the reference's state dispatch (base.py:423-500) on an already captured frame."""

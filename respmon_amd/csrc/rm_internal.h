@@ -12,7 +12,7 @@
 //   rm_roi.hip            heatmap -> ROI, sparse heatmap packets                         (base.py:563-575)
 //   rm_locate.hip         rm_locate, rm_locate_submit / rm_locate_result                 (base.py:547-601)
 //   rm_comm.hip           RCCL behind the C-ABI                                          
-//   rm_motion.hip         ROI mean / crop, corners, LK, PCA; the ROI means of several subjects (base.py:354-407; rm_subjects.h)
+//   rm_motion.hip         ROI mean / crop, corners, LK, PCA; the ROI means and the LK flow of several subjects (base.py:354-407; rm_subjects.h, rm_flow_multi.h)
 //   rm_window.hip         rm_window_*: a ring of per-frame pyramid rows, relocated in place          (base.py:409-513 without the refill)
 //   rm_magnify.hip        rm_magnify, rm_magnify_bgr: frames + band-passed motion in one pass            (transforms.py:170, 181; rm_magnify.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
@@ -136,7 +136,7 @@ struct DebugKnobs {
     int tile_sum_half = -1;       // 0 / 1: k_tile_sum works on whole tiles / half tiles whatever the number of heavy tiles (-1: by that number)
     long long store_default_slots = 0;   // > 0: slots the value store starts with before any selection has made it grow (default 16 384)
     long long store_slots = 0;    // > 0: capacity of the value store in (tile, frame) slots (forces the overflow path)
-    long long flow_clip_bytes = 0;   // > 0: workspace cap of one chunk of rm_flow_clip (default 256 MiB): a chunk holds max(1, cap / slot - 1) frames, slot = 5 bytes per pixel of every LK pyramid level of the ROI
+    long long flow_clip_bytes = 0;   // > 0: workspace cap of one chunk of rm_flow_clip / rm_flow_multi_clip (default 256 MiB): a chunk holds max(1, cap / slot - 1) frames, slot = 5 bytes per pixel of every LK pyramid level of the ROI (summed over the subjects that still have points)
 };
 
 // pinned result areas of ONE ROI extraction in flight

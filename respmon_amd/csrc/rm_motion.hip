@@ -1,6 +1,7 @@
-// respmon_amd/csrc/rm_motion.hip -- ROI reductions and motion extraction (base.py:354-407)
+// respmon_amd/csrc/rm_motion.hip -- ROI reductions and motion extraction (base.py:354-407), for one subject and for several
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_flow_multi.h"
 
 using namespace rm;
 
@@ -429,6 +430,265 @@ extern "C" int rm_flow_clip(rm_ctx *ctx, rm_flow_state *state, const void *frame
     fs.pyr_levels[cur_side] = max_level; fs.deriv_levels[cur_side] = -1;
     fs.npts = n_good_host[N - 1];
     fs.flip ^= 1;
+    return RM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// several subjects per clip (rm_flow_multi.h): K rm_flow_clip calls, K rm_pca_reduce_windows calls as one call each
+// ------------------------------------------------------------------------------------------
+template <typename Tin>
+static void launch_multi_crop(const void *frames, size_t px, int W, const FlowSubject *tab, dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_flow_multi_crop<Tin>), grid, dim3(256), 0, s, (const Tin *)frames, px, W, tab);
+}
+static int flow_multi_crop(const void *frames, int dtype, int n, int H, int W, const FlowSubject *tab, int nsub, size_t max_px, hipStream_t s)
+{
+    const size_t px = (size_t)H * W;
+    const dim3 grid(nblk(max_px, 256, 1024), (unsigned)n, (unsigned)nsub);
+    switch (dtype) {
+    case RM_U8: launch_multi_crop<uint8_t>(frames, px, W, tab, grid, s); break;
+    case RM_F16: launch_multi_crop<__half>(frames, px, W, tab, grid, s); break;
+    case RM_F32: launch_multi_crop<float>(frames, px, W, tab, grid, s); break;
+    default: launch_multi_crop<double>(frames, px, W, tab, grid, s); break;
+    }
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
+// Subject k on states[k] with rectangle k, exactly as K rm_flow_clip calls would leave outputs and states.  The subjects that still
+// have points ("live") share the chunks of one clip walk: one chunk length C for all, their images and derivatives in two arenas of
+// the context, their points side by side under one global index (pt0 = prefix sum), so position and life pass from chunk to chunk
+// through carry buffers of the whole call.  A subject without points only gets the crop of the clip's last frame (one extra launch
+// for all of them).  Launches per chunk: 1 crop + (levels - 1) pyrDown + levels Scharr + 1 tracker + 1 or 2 finish (+ 1 carry).
+extern "C" int rm_flow_multi_clip(rm_ctx *ctx, rm_flow_state *const *states, const void *frames, int dtype, int N, int H, int W, const int32_t *rois,
+                                  int K, int win_w, int win_h, int max_level, int max_count, double epsilon, float *mean_xy_host,
+                                  int32_t *n_good_host, void *stream)
+{
+    if (!ctx || !states || !frames || !rois || !mean_xy_host || !n_good_host || N < 1 || H < 1 || W < 1 || K < 1 || K > RM_MAX_ROIS ||
+        !valid_dtype(dtype) || win_w < 3 || win_h < 3 || max_level < 0 || (long long)N * K > 0x7fffffffll)
+        return fail(RM_E_BADARG, "rm_flow_multi_clip: bad argument (1 <= K <= %d)", RM_MAX_ROIS);
+    // the whole call is refused before anything is enqueued or any state is touched: argument errors of every subject first ...
+    for (int k = 0; k < K; ++k) {
+        const int32_t *r = rois + 4 * k;
+        if (!states[k]) return fail(RM_E_BADARG, "rm_flow_multi_clip: subject %d has no flow state (NULL)", k);
+        if (!roi_ok(H, W, r[0], r[1], r[2], r[3]))
+            return fail(RM_E_BADARG, "rm_flow_multi_clip: rectangle %d (%d, %d, %d, %d) does not lie inside the %d x %d frame", k, r[0], r[1], r[2], r[3], W, H);
+        const FlowState &fs = states[k]->fs;
+        if (!fs.begun || r[2] != fs.w || r[3] != fs.h)
+            return fail(RM_E_BADARG, "rm_flow_multi_clip: rm_flow_begin has not been called on the state of subject %d for this ROI size", k);
+        if (states[k]->device != ctx->device) return fail(RM_E_BADARG, "rm_flow_multi_clip: the flow state of subject %d belongs to another device", k);
+        for (int j = 0; j < k; ++j)
+            if (states[j] == states[k]) return fail(RM_E_BADARG, "rm_flow_multi_clip: subject %d uses the flow state of subject %d", k, j);
+    }
+    // ... then the limits rm_flow_clip meets for a subject that still has points
+    for (int k = 0; k < K; ++k) {
+        if (states[k]->fs.npts == 0) continue;
+        if (win_w * win_h > LK_MAX_WIN) return fail(RM_E_UNSUPPORTED, "rm_flow_multi_clip: winSize too large (subject %d)", k);
+        if (lk_max_level(rois[4 * k + 3], rois[4 * k + 2], win_w, win_h, max_level) + 1 > LK_MAX_LEVELS)
+            return fail(RM_E_UNSUPPORTED, "rm_flow_multi_clip: too many pyramid levels (subject %d)", k);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t frame_bytes = (size_t)H * W * dtype_size(dtype);
+    if (max_count < 0) max_count = 0;
+    if (max_count > 100) max_count = 100;
+    if (epsilon < 0) epsilon = 0;
+    if (epsilon > 10) epsilon = 10;
+    epsilon *= epsilon;
+
+    // table rows: the live subjects first (row j = subject live[j]), then the others
+    std::vector<int> live, dead;
+    for (int k = 0; k < K; ++k) (states[k]->fs.npts > 0 ? live : dead).push_back(k);
+    const int KL = (int)live.size(), KD = (int)dead.size();
+    std::vector<FlowSubject> tab((size_t)K);
+    std::memset(tab.data(), 0, sizeof(FlowSubject) * (size_t)K);
+    size_t slot_bytes = 0, max_px[LK_MAX_LEVELS] = {0}, dead_px = 0;
+    int P = 0, top_levels = 0, max_staged = 0;
+    bool any_seq = false;
+    for (int j = 0; j < KL; ++j) {
+        const int k = live[j];
+        FlowSubject &S = tab[j];
+        S.x = rois[4 * k]; S.y = rois[4 * k + 1]; S.w = rois[4 * k + 2]; S.h = rois[4 * k + 3];
+        S.npts = states[k]->fs.npts; S.pt0 = P;
+        P += S.npts;
+        S.L.n = lk_max_level(S.h, S.w, win_w, win_h, max_level) + 1;
+        for (int l = 0, sh = S.h, sw = S.w; l < S.L.n; ++l, sh = (sh + 1) / 2, sw = (sw + 1) / 2) {
+            S.L.h[l] = sh; S.L.w[l] = sw; S.L.stride[l] = (size_t)sh * sw;
+            slot_bytes += S.L.stride[l] * (1 + 2 * sizeof(short));
+            max_px[l] = std::max(max_px[l], S.L.stride[l]);
+        }
+        top_levels = std::max(top_levels, S.L.n);
+        if (S.npts <= FLOW_FINISH_MAX) max_staged = std::max(max_staged, S.npts); else any_seq = true;
+    }
+    for (int j = 0; j < KD; ++j) {
+        const int k = dead[j];
+        FlowSubject &S = tab[KL + j];
+        S.x = rois[4 * k]; S.y = rois[4 * k + 1]; S.w = rois[4 * k + 2]; S.h = rois[4 * k + 3];
+        dead_px = std::max(dead_px, (size_t)S.w * S.h);
+    }
+    const long long cap = ctx->dbg.flow_clip_bytes > 0 ? ctx->dbg.flow_clip_bytes : FLOW_CLIP_BYTES;
+    const int C = KL ? (int)std::max<long long>(1, std::min<long long>(std::min(N, FLOW_CLIP_MAX_CHUNK), cap / (long long)slot_bytes - 1)) : 1;
+
+    // every buffer the call needs, of the context (arenas, point arrays, table) and of the states, before anything is enqueued
+    std::string err;
+    int rc;
+    uint8_t *img_arena = nullptr, *d_st = nullptr, *carry_a[2] = {nullptr, nullptr}, *d_tab_bytes = nullptr;
+    short *der_arena = nullptr;
+    float *d_pos = nullptr, *d_res = nullptr, *carry_p[2] = {nullptr, nullptr};
+    const size_t tab_bytes = sizeof(FlowSubject) * (size_t)K, up_bytes = tab_bytes + sizeof(int) * (size_t)P;
+    if ((rc = ctx->flow.get("fm_table", up_bytes, (void **)&d_tab_bytes, err)) < 0) return fail(rc, "%s", err.c_str());
+    const FlowSubject *d_tab = (const FlowSubject *)d_tab_bytes;
+    const int *d_pt_subject = (const int *)(d_tab_bytes + tab_bytes);
+    if (KL) {
+        size_t img_px = 0;   // pixels of one image of every level of every live subject
+        for (int j = 0; j < KL; ++j) for (int l = 0; l < tab[j].L.n; ++l) img_px += tab[j].L.stride[l];
+        if ((rc = ctx->flow.get("fm_img", img_px * (size_t)(C + 1), (void **)&img_arena, err)) < 0) return fail(rc, "%s", err.c_str());
+        if ((rc = ctx->flow.get("fm_deriv", img_px * 2 * sizeof(short) * (size_t)C, (void **)&der_arena, err)) < 0) return fail(rc, "%s", err.c_str());
+        if ((rc = ctx->flow.get("fm_pos", sizeof(float) * 2 * (size_t)P * C, (void **)&d_pos, err)) < 0) return fail(rc, "%s", err.c_str());
+        if ((rc = ctx->flow.get("fm_status", (size_t)P * C, (void **)&d_st, err)) < 0) return fail(rc, "%s", err.c_str());
+        if ((rc = ctx->flow.get("fm_res", sizeof(float) * 4 * (size_t)N * KL, (void **)&d_res, err)) < 0) return fail(rc, "%s", err.c_str());
+        for (int i = 0; i < 2; ++i) {
+            if ((rc = ctx->flow.get(i ? "fm_carry_pts_b" : "fm_carry_pts_a", sizeof(float) * 2 * (size_t)P, (void **)&carry_p[i], err)) < 0) return fail(rc, "%s", err.c_str());
+            if ((rc = ctx->flow.get(i ? "fm_carry_alive_b" : "fm_carry_alive_a", (size_t)P, (void **)&carry_a[i], err)) < 0) return fail(rc, "%s", err.c_str());
+        }
+    }
+    std::vector<uint8_t *> st_prev((size_t)K, nullptr);                  // [k]: the crop the subject tracks from
+    std::vector<float *> st_pts((size_t)K, nullptr);                     // [k]: its points
+    std::vector<uint8_t *> st_cur((size_t)K * LK_MAX_LEVELS, nullptr);   // [k][l]: level l of the "current" side
+    size_t img_off = 0, der_off = 0;
+    for (int j = 0; j < K; ++j) {
+        const int k = j < KL ? live[j] : dead[j - KL];
+        FlowState &fs = states[k]->fs;
+        FlowSubject &S = tab[j];
+        const int cur_side = fs.flip ^ 1;
+        RM_TRY(flow_state_crop(fs, cur_side, &st_cur[(size_t)k * LK_MAX_LEVELS]));
+        if (j >= KL) { S.crop_dst = st_cur[(size_t)k * LK_MAX_LEVELS]; continue; }
+        float *pa = nullptr, *pb = nullptr;
+        RM_TRY(flow_state_crop(fs, fs.flip, &st_prev[k]));
+        RM_TRY(flow_state_pts(fs, &pa, &pb));
+        st_pts[k] = fs.flip ? pb : pa;
+        S.next_pts = fs.flip ? pa : pb;
+        for (int l = 0; l < S.L.n; ++l) {
+            if (l > 0 && (rc = flow_side_buf(fs, cur_side, "pyr", l, S.L.stride[l], (void **)&st_cur[(size_t)k * LK_MAX_LEVELS + l], err)) < 0)
+                return fail(rc, "%s", err.c_str());
+            S.L.prev[l] = img_arena + img_off; S.L.next[l] = S.L.prev[l] + S.L.stride[l]; S.L.deriv[l] = der_arena + der_off;
+            img_off += S.L.stride[l] * (size_t)(C + 1); der_off += S.L.stride[l] * 2 * (size_t)C;
+        }
+        S.crop_dst = const_cast<uint8_t *>(S.L.next[0]);
+    }
+    std::vector<uint8_t> up(up_bytes);
+    std::memcpy(up.data(), tab.data(), tab_bytes);
+    int *pt_subject = (int *)(up.data() + tab_bytes);
+    for (int j = 0; j < KL; ++j) for (int i = 0; i < tab[j].npts; ++i) pt_subject[tab[j].pt0 + i] = j;
+
+    for (size_t i = 0; i < (size_t)N * K; ++i) { mean_xy_host[2 * i] = mean_xy_host[2 * i + 1] = 0.f; n_good_host[i] = 0; }
+    HIP_TRY(hipMemcpyAsync(d_tab_bytes, up.data(), up_bytes, hipMemcpyHostToDevice, s));
+    if (KD)   // nothing to track: the previous image advances to the clip's last frame (base.py:381)
+        RM_TRY(flow_multi_crop((const char *)frames + (size_t)(N - 1) * frame_bytes, dtype, 1, H, W, d_tab + KL, KD, dead_px, s));
+    std::vector<float> res;
+    if (KL) {
+        for (int j = 0; j < KL; ++j) {
+            const int k = live[j];
+            HIP_TRY(hipMemcpyAsync(carry_p[0] + 2 * (size_t)tab[j].pt0, st_pts[k], sizeof(float) * 2 * (size_t)tab[j].npts, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(const_cast<uint8_t *>(tab[j].L.prev[0]), st_prev[k], tab[j].L.stride[0], hipMemcpyDeviceToDevice, s));
+        }
+        HIP_TRY(hipMemsetAsync(carry_a[0], 1, (size_t)P, s));
+        const size_t finish_lds = 2 * sizeof(float) * (size_t)flow_finish_pitch(max_staged);
+        int last = 0;   // the image of the chunk just done that holds its last frame
+        for (int c0 = 0, c = 0; c0 < N; c0 += C, ++c) {
+            const int n = std::min(C, N - c0);
+            const bool final_chunk = c0 + n == N;
+            // frame-parallel front: crops into images 1 .. n, the pyramids of images 0 .. n, the derivatives of images 0 .. n - 1
+            RM_TRY(flow_multi_crop((const char *)frames + (size_t)c0 * frame_bytes, dtype, n, H, W, d_tab, KL, max_px[0], s));
+            for (int l = 1; l < top_levels; ++l)
+                hipLaunchKernelGGL(k_flow_multi_pyr_down<>, dim3((unsigned)((max_px[l] + 255) / 256), n + 1, KL), dim3(256), 0, s, d_tab, l);
+            for (int l = 0; l < top_levels; ++l)
+                hipLaunchKernelGGL(k_flow_multi_scharr<>, dim3((unsigned)((max_px[l] + 255) / 256), n, KL), dim3(256), 0, s, d_tab, l);
+            // one wave per (subject, point), one workgroup per (frame, subject)
+            const float *start = carry_p[c & 1]; const uint8_t *start_alive = carry_a[c & 1];
+            if (win_w * win_h <= 256)
+                hipLaunchKernelGGL(k_lk_track_multi_clip<4>, dim3(P), dim3(64), 0, s, d_tab, d_pt_subject, n, start, start_alive, P, win_w, win_h, max_count,
+                                   epsilon, d_pos, d_st, carry_p[(c + 1) & 1], carry_a[(c + 1) & 1]);
+            else
+                hipLaunchKernelGGL(k_lk_track_multi_clip<16>, dim3(P), dim3(64), 0, s, d_tab, d_pt_subject, n, start, start_alive, P, win_w, win_h, max_count,
+                                   epsilon, d_pos, d_st, carry_p[(c + 1) & 1], carry_a[(c + 1) & 1]);
+            float *res_c = d_res + 4 * (size_t)c0 * KL;
+            if (max_staged > 0)
+                hipLaunchKernelGGL(k_flow_finish_multi<>, dim3(n, KL), dim3(64), finish_lds, s, d_tab, start, d_pos, d_st, P, n, res_c, final_chunk ? 1 : 0);
+            if (any_seq)
+                hipLaunchKernelGGL(k_flow_finish_multi_seq<>, dim3(n, KL), dim3(1), 0, s, d_tab, start, d_pos, d_st, P, n, res_c, final_chunk ? 1 : 0);
+            LAUNCH_CHECK();
+            last = n;
+            if (!final_chunk) {
+                hipLaunchKernelGGL(k_flow_multi_carry<>, dim3(nblk(max_px[0], 256, 1024), KL), dim3(256), 0, s, d_tab, n);
+                LAUNCH_CHECK();
+            }
+        }
+        // the state the next call starts from: the last crop with its pyramid (derivatives are built by the call that tracks from it)
+        for (int j = 0; j < KL; ++j)
+            for (int l = 0; l < tab[j].L.n; ++l)
+                HIP_TRY(hipMemcpyAsync(st_cur[(size_t)live[j] * LK_MAX_LEVELS + l], tab[j].L.prev[l] + (size_t)last * tab[j].L.stride[l], tab[j].L.stride[l],
+                                       hipMemcpyDeviceToDevice, s));
+        res.resize(4 * (size_t)N * KL);
+        HIP_TRY(hipMemcpyAsync(res.data(), d_res, sizeof(float) * 4 * (size_t)N * KL, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(stream_wait(s));   // (the table's host memory may go now as well)
+    for (int j = 0; j < KL; ++j) {
+        const int k = live[j];
+        for (int i = 0; i < N; ++i) {
+            const float *r = &res[4 * ((size_t)i * KL + j)];
+            mean_xy_host[2 * ((size_t)i * K + k)] = r[0]; mean_xy_host[2 * ((size_t)i * K + k) + 1] = r[1]; n_good_host[(size_t)i * K + k] = (int)r[2];
+        }
+    }
+    for (int j = 0; j < K; ++j) {
+        const int k = j < KL ? live[j] : dead[j - KL];
+        FlowState &fs = states[k]->fs;
+        const int cur_side = fs.flip ^ 1;
+        fs.pyr_levels[cur_side] = j < KL ? tab[j].L.n - 1 : 0; fs.deriv_levels[cur_side] = -1;
+        if (j < KL) fs.npts = n_good_host[(size_t)(N - 1) * K + k];
+        fs.flip ^= 1;
+    }
+    return RM_OK;
+}
+
+// seg[k] = {first row of list k inside motion, its number of rows n_k, first_k}: list k's outputs are rm_pca_reduce_windows(its rows,
+// n_k, first_k, window), one list after the other in out.  The lists may leave gaps between them but may not overlap.
+extern "C" int rm_pca_reduce_windows_multi(rm_ctx *ctx, const float *motion, const int32_t *seg, int K, int window, double *out, void *stream)
+{
+    if (!ctx || !seg || K < 1 || K > RM_MAX_ROIS || window < 1) return fail(RM_E_BADARG, "rm_pca_reduce_windows_multi: bad argument (1 <= K <= %d)", RM_MAX_ROIS);
+    long long rows = 0, nout = 0;
+    for (int k = 0; k < K; ++k) {
+        const long long row0 = seg[3 * k], n = seg[3 * k + 1], first = seg[3 * k + 2];
+        if (row0 < 0 || n < 0 || first < 0 || first > n || row0 + n > 0x7fffffffll)
+            return fail(RM_E_BADARG, "rm_pca_reduce_windows_multi: bad segment %d (first row %lld, %lld rows, first %lld)", k, row0, n, first);
+        for (int j = 0; j < k; ++j)
+            if (n > 0 && seg[3 * j + 1] > 0 && row0 < (long long)seg[3 * j] + seg[3 * j + 1] && seg[3 * j] < row0 + n)
+                return fail(RM_E_BADARG, "rm_pca_reduce_windows_multi: segments %d and %d overlap", j, k);
+        rows = std::max(rows, n > 0 ? row0 + n : 0);
+        nout += n - first;
+    }
+    if (nout > 0x7fffffffll || (rows > 0 && !motion) || (nout > 0 && !out)) return fail(RM_E_BADARG, "rm_pca_reduce_windows_multi: bad argument");
+    if (nout == 0) return RM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // one upload: the rows, behind them the (first row of the list, row inside the list) pair of every output
+    const size_t rows_bytes = (sizeof(float) * 2 * (size_t)rows + 7) / 8 * 8, map_bytes = sizeof(int) * 2 * (size_t)nout;
+    std::vector<uint8_t> up(rows_bytes + map_bytes);
+    std::memcpy(up.data(), motion, sizeof(float) * 2 * (size_t)rows);
+    int *map = (int *)(up.data() + rows_bytes);
+    for (int k = 0; k < K; ++k)
+        for (int j = seg[3 * k + 2]; j < seg[3 * k + 1]; ++j) { *map++ = seg[3 * k]; *map++ = j; }
+    std::string err;
+    uint8_t *d_in = nullptr;
+    double *d_o = nullptr;
+    int rc;
+    if ((rc = ctx->flow.get("pcawm_in", up.size(), (void **)&d_in, err)) < 0) return fail(rc, "%s", err.c_str());
+    if ((rc = ctx->flow.get("pcawm_out", sizeof(double) * (size_t)nout, (void **)&d_o, err)) < 0) return fail(rc, "%s", err.c_str());
+    HIP_TRY(hipMemcpyAsync(d_in, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_pca_reduce_windows_multi<>, dim3((unsigned)nout), dim3(64), 0, s, (const float *)d_in, (const int *)(d_in + rows_bytes), window, d_o);
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(out, d_o, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
     return RM_OK;
 }
 

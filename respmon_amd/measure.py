@@ -6,6 +6,8 @@ capture / calibration state machine; respmon_amd.subjects.SubjectTracker holds o
 A user of the mixin provides: fps, freq_max, filter_order, gaussian_cutoff, peak_minimum_sample_distance, measure_buffer_length,
 measure_initialization_length, save_all_data, all_data, disable_error_detection, the deques data / t / freq, the list `buffers` of
 the deques the pop-left rule applies to, and -- unless disable_error_detection is set -- detect_errors() / trigger_error().
+For the 'flow' method's clips (_flow_clip_rows / _flow_clip_replay) also the deque motion_data and _flow_n, the number of points the
+tracking session still has.
 """
 import numpy as np
 
@@ -66,3 +68,30 @@ class BreathSignal:
             self.measure()
             if not self.disable_error_detection and self.detect_errors():
                 self.trigger_error("error detection found poor signal")
+
+    # ------------------------------------------------------------------ a clip of extract_motion('flow'), base.py:371-407
+    def _flow_clip_rows(self, mean, n_good):
+        """(rows, first): motion_data followed by the rows a tracked clip appends to it -- the frames in front of the one that loses
+        the last point -- and the index of the first new row.  The deque holds at most measure_buffer_length rows (popleft before
+        every frame), so frame i's PCA runs over that many rows ending in its own: pca_reduce_windows(rows, first, that length)."""
+        k = 0
+        while k < len(n_good) and n_good[k] > 0:
+            k += 1
+        first = len(self.motion_data)
+        rows = np.array(list(self.motion_data) + [[mean[i][0], mean[i][1]] for i in range(k)], dtype=np.float32).reshape(-1, 2)
+        return rows, first
+
+    def _flow_clip_replay(self, mean, n_good, pca):
+        """value(i) = what extract_motion() returns for frame i of a clip tracked from a state with points: mean [N,2] and n_good [N]
+        of the clip, pca the values of its new rows.  To be called once per frame, in order, behind the popleft rule."""
+        def value(i):
+            if self._flow_n == 0:
+                return np.nan
+            self._flow_n = int(n_good[i])
+            if self._flow_n == 0:
+                return np.nan                                               # base.py:385-386 (the object np.nan: detect_errors tests identity)
+            self.motion_data.append([mean[i][0], mean[i][1]])               # base.py:389
+            if len(self.motion_data) >= 2:
+                return float(pca[i])                                        # base.py:396-405
+            return 0.0
+        return value

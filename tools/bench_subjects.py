@@ -6,6 +6,8 @@ alternating.
 1080p uint8, N = 128 frames, K = 1, 4, 16 subjects with 351x235 ROIs:
   roi_mean  one rm_roi_mean_multi_clip call against K rm_roi_mean_clip calls (outputs asserted equal before anything is timed)
   locate    rm_locate_multi(max_rois = K) against rm_locate on a buffer with sixteen breathing blobs (entry 0 asserted equal)
+  flow      one rm_flow_multi_clip + one rm_pca_reduce_windows_multi against K rm_flow_clip + K rm_pca_reduce_windows, 100 corners per
+            subject on textured frames, K fresh states per repetition (begun outside the timed part; outputs asserted equal first)
 Prints one JSON line: milliseconds per call of both forms (the median of the alternating repetitions).  No threshold is set on
 these figures: they are recorded."""
 import argparse
@@ -43,6 +45,46 @@ def timed(torch, fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
+def flow_section(a, torch, be, res):
+    from respmon_amd import synth
+    N, H, W = a.frames, 1080, 1920
+    render = synth.synth_texture(H, W, seed=4321)
+    tex = torch.from_numpy(np.stack([render(1.5 * np.sin(2 * np.pi * 0.4 * t / 30), 0.5 * np.sin(2 * np.pi * 0.4 * t / 30 + np.pi / 3))
+                                     for t in range(N + 1)])).cuda()
+    lk = dict(winSize=(15, 15), maxLevel=2, criteria=(3, 10, 0.03))
+    window = 128
+    for K in KS:
+        rois = rois_for(K, H, W)
+
+        def begin():
+            states = [be.flow_state() for _ in rois]
+            npts = [len(be.flow_begin(st, tex[0], *r, 100, 0.3, 7, 7)) for st, r in zip(states, rois)]
+            return states, npts
+
+        def multi(states):
+            mean, ng = be.flow_multi_clip(states, tex[1:], rois, **lk)
+            assert (ng > 0).all()
+            return mean, ng, be.pca_reduce_windows_multi([mean[:, k] for k in range(K)], [0] * K, window)
+
+        def loop(states):
+            out = [be.flow_clip(st, tex[1:], *r, **lk) for st, r in zip(states, rois)]
+            return (np.stack([m for m, _ in out], axis=1), np.stack([n for _, n in out], axis=1),
+                    [be.pca_reduce_windows(m, 0, window) for m, _ in out])
+
+        (sm, npts), (sl, _) = begin(), begin()
+        gm, gl = multi(sm), loop(sl)
+        assert np.array_equal(gm[0], gl[0]) and np.array_equal(gm[1], gl[1]), "rm_flow_multi_clip differs from rm_flow_clip"
+        assert all(np.array_equal(x, y) for x, y in zip(gm[2], gl[2])), "rm_pca_reduce_windows_multi differs from rm_pca_reduce_windows"
+        tm, tl = [], []
+        for _ in range(a.reps):
+            sl, _ = begin()
+            tl.append(timed(torch, lambda: loop(sl))[0])
+            sm, _ = begin()
+            tm.append(timed(torch, lambda: multi(sm))[0])
+        res["flow"]["K%d" % K] = {"points": npts, "multi_ms": statistics.median(tm), "k_calls_ms": statistics.median(tl), "multi_ms_all": tm,
+                                  "k_calls_ms_all": tl}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=128)
@@ -58,7 +100,7 @@ def main():
     vid = synth.synth_breathing_dense(N, H, W, seed=4321, noise=0.02, centers=centers, sigma=(0.05, 0.04), phase_step=0.0, workers=16)
     frames = torch.from_numpy(vid).cuda()
     res = {"tool": "bench_subjects", "device": torch.cuda.get_device_name(0), "frames": N, "shape": [H, W], "roi": [ROI_W, ROI_H],
-           "roi_mean": {}, "locate": {}}
+           "roi_mean": {}, "locate": {}, "flow": {}}
     for K in KS:
         rois = rois_for(K, H, W)
         multi = lambda: be.roi_mean_multi_clip(frames, rois)
@@ -80,6 +122,7 @@ def main():
             tm.append(timed(torch, many)[0])
         res["locate"]["K%d" % K] = {"rois_found": len(rk), "multi_ms": statistics.median(tm), "single_ms": statistics.median(tl),
                                     "multi_ms_all": tm, "single_ms_all": tl}
+    flow_section(a, torch, be, res)
     line = json.dumps(res)
     print(line, flush=True)
     if a.out:
