@@ -403,9 +403,12 @@ int rm_flow_points(rm_ctx *ctx, rm_flow_state *state, float *pts_host, int cap, 
  *        split anywhere.  A state with no points left only advances its previous image (mean 0, n_good 0 for every frame).
  *        Crops, pyramids and derivatives of all frames are built frame-parallel, one wavefront per point then walks the frames in
  *        order; the clip is worked through in chunks whose workspace (about 6.7 bytes per ROI pixel and frame) stays under 256 MiB.
+ *        It is the K == 1 entry of rm_flow_multi_clip's driver: the chunk workspace (images, derivatives, positions, carry buffers)
+ *        belongs to the context, shared by every state used with it -- a context is not thread-safe, use one per stream / GPU --
+ *        while the state keeps the last crop with its pyramid, its points and its counters.
  *      rm_pca_reduce_windows: for every j in [first, n), out_host[j - first] = rm_pca_reduce of rows max(0, j + 1 - window) .. j of
  *        motion_host[n][2] (0.0 below two rows): the values extract_motion returns while the motion_data deque of base.py:473-475
- *        holds at most `window` rows. */
+ *        holds at most `window` rows.  The K == 1 case of rm_pca_reduce_windows_multi. */
 int rm_roi_mean_clip(rm_ctx *ctx, const void *frames_dev, int dtype, int N, int H, int W, int x, int y, int w, int h,
                      double *out_host, void *stream);
 int rm_flow_clip(rm_ctx *ctx, rm_flow_state *state, const void *frames_dev, int dtype, int N, int H, int W, int x, int y, int w, int h,
@@ -431,12 +434,12 @@ int rm_roi_mean_multi_clip(rm_ctx *ctx, const void *frames_dev, int dtype, int N
  *        first offending subject.  RM_E_BADARG: K outside 1..RM_MAX_ROIS, N < 1, NULL pointers (a NULL entry of states_host
  *        included), a dtype that is no frame dtype, win_w or win_h < 3, max_level < 0, N * K beyond int, a rectangle outside the
  *        frame, a state that is not begun, was begun for another ROI size or belongs to another device, the same state twice.
- *        RM_E_UNSUPPORTED where rm_flow_clip returns it for a subject that still has points.  K == 1 equals rm_flow_clip.
+ *        RM_E_UNSUPPORTED where rm_flow_step returns it for a subject that still has points.  K == 1 is rm_flow_clip.
  *      rm_pca_reduce_windows_multi: K motion lists in one call.  motion_host holds the rows of all lists; seg_host[k] = {first row
  *        of list k, its number of rows n_k, first_k}; out_host takes, list after list, the n_k - first_k values
  *        rm_pca_reduce_windows(rows of k, n_k, first_k, window) returns, bit for bit.  One upload, one launch, one download, one
  *        wait.  A list with first_k == n_k contributes nothing.  RM_E_BADARG: K outside 1..RM_MAX_ROIS, window < 1, a negative
- *        entry, first_k > n_k, lists that overlap.  K == 1 equals rm_pca_reduce_windows. */
+ *        entry, first_k > n_k, lists that overlap.  K == 1 is rm_pca_reduce_windows. */
 int rm_flow_multi_clip(rm_ctx *ctx, rm_flow_state *const *states_host /* [K] */, const void *frames_dev, int dtype,
                        int N, int H, int W, const int32_t *rois_host /* [K][4] x,y,w,h */, int K,
                        int win_w, int win_h, int max_level, int max_count, double epsilon,

@@ -218,7 +218,7 @@ inline int flow_good_features(FlowWorkspace &ws, const uint8_t *img, int h, int 
 // calcOpticalFlowPyrLK  
 // ----------------------------------------------------------------------------------------
 // uint8 pyrDown: integer 5-tap, (sum + 128) >> 8, BORDER_REFLECT_101
-// (output pixel i of one image; shared by the per-image kernel and the per-clip kernel of rm_flow_clip.h)
+// (output pixel i of one image; shared by the per-image kernel and the per-clip kernel of rm_flow_multi.h)
 __device__ __forceinline__ void pyr_down_u8_px(const uint8_t *src, int h, int w, uint8_t *dst, int dh, int dw, int i)
 {
     if (i >= dh * dw) return;
@@ -265,7 +265,7 @@ struct LKLevels {
     int h[LK_MAX_LEVELS], w[LK_MAX_LEVELS];
     const uint8_t *prev[LK_MAX_LEVELS], *next[LK_MAX_LEVELS];
     const short *deriv[LK_MAX_LEVELS];
-    // a clip's images lie stride[l] pixels apart (rm_flow_clip.h): frame f tracks from prev[l] + f * stride[l] to next[l] + f * stride[l]
+    // a clip's images lie stride[l] pixels apart (rm_flow_multi.h): frame f tracks from prev[l] + f * stride[l] to next[l] + f * stride[l]
     // with the derivatives at deriv[l] + 2 * f * stride[l].  Unused (frame 0) by the one-pair entry points.
     size_t stride[LK_MAX_LEVELS];
 };
@@ -444,6 +444,14 @@ inline int lk_max_level(int h, int w, int win_w, int win_h, int max_level)
     return max_level;
 }
 
+// calcOpticalFlowPyrLK's termination criteria as OpenCV clamps them; epsilon comes back squared (the tracker compares squared steps)
+inline void lk_clamp_criteria(int &max_count, double &epsilon)
+{
+    max_count = std::min(std::max(max_count, 0), 100);
+    epsilon = std::min(std::max(epsilon, 0.0), 10.0);
+    epsilon *= epsilon;
+}
+
 // device half of flow_pyr_lk: pyramids, derivatives and the tracking kernel; points in / out and status stay on the device,
 // nothing is copied and the stream is not waited for.  Returns the number of pyramid levels above level 0 that were used.
 inline int flow_pyr_lk_dev(FlowWorkspace &ws, const uint8_t *prev, const uint8_t *next, int h, int w, const float *d_in, int npts,
@@ -451,11 +459,7 @@ inline int flow_pyr_lk_dev(FlowWorkspace &ws, const uint8_t *prev, const uint8_t
                            hipStream_t s, std::string &err)
 {
     if (win_w * win_h > LK_MAX_WIN) { err = "winSize too large"; return RM_E_UNSUPPORTED; }
-    if (max_count < 0) max_count = 0;
-    if (max_count > 100) max_count = 100;
-    if (epsilon < 0) epsilon = 0;
-    if (epsilon > 10) epsilon = 10;
-    epsilon *= epsilon;
+    lk_clamp_criteria(max_count, epsilon);
     max_level = lk_max_level(h, w, win_w, win_h, max_level);
     if (max_level + 1 > LK_MAX_LEVELS) { err = "too many pyramid levels"; return RM_E_UNSUPPORTED; }
     LKLevels L = {};
@@ -511,7 +515,7 @@ inline int flow_pyr_lk(FlowWorkspace &ws, const uint8_t *prev, const uint8_t *ne
 // lane 0 adds the differences in point order from LDS.  (One THREAD walking global memory took 150 us for 1 000 points.)
 constexpr int FLOW_FINISH_MAX = 6000;   // points whose differences fit the LDS staging (2 floats each)
 __host__ __device__ __forceinline__ int flow_finish_pitch(int n) { return (n + 3) & ~3; }   // floats per staged component
-// (the wave's work; next_pts may be null: the frames of a clip that nothing tracks from, rm_flow_clip.h)
+// (the wave's work; next_pts may be null: the frames of a clip that nothing tracks from, rm_flow_multi.h)
 __device__ __forceinline__ void flow_finish_wave(const float *o, const float *nw, const uint8_t *st, int n, float *res, float *next_pts, float *s_d)
 {
     const int lane = threadIdx.x;
@@ -591,11 +595,7 @@ inline int flow_track_resident(FlowState &fs, int prev_side, int cur_side, const
 {
     const int h = fs.h, w = fs.w;
     if (win_w * win_h > LK_MAX_WIN) { err = "winSize too large"; return RM_E_UNSUPPORTED; }
-    if (max_count < 0) max_count = 0;
-    if (max_count > 100) max_count = 100;
-    if (epsilon < 0) epsilon = 0;
-    if (epsilon > 10) epsilon = 10;
-    epsilon *= epsilon;
+    lk_clamp_criteria(max_count, epsilon);
     max_level = lk_max_level(h, w, win_w, win_h, max_level);
     if (max_level + 1 > LK_MAX_LEVELS) { err = "too many pyramid levels"; return RM_E_UNSUPPORTED; }
     LKLevels L = {};

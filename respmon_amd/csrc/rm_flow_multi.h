@@ -1,20 +1,25 @@
-// respmon_amd/csrc/rm_flow_multi.h -- extract_motion('flow') of SEVERAL subjects over a resident clip in one call
-// (rm_flow_multi_clip, rm_pca_reduce_windows_multi; rm_motion.hip).  The tracks of different subjects are as independent as the
-// tracks of different points, so K subjects share every launch of rm_flow_clip.h's scheme:
-//   frame-parallel front   the grid is (pixel block, image of the chunk, subject); a workgroup beyond its subject's pixel or level
-//                          count leaves at once
-//   tracker                one wavefront per (subject, point), the grid exactly the total point count
-//   finish                 one workgroup per (frame, subject)
+// respmon_amd/csrc/rm_flow_multi.h -- extract_motion('flow') over a whole resident clip in one call, for one subject or several
+// (rm_flow_clip = the K == 1 entry, rm_flow_multi_clip, rm_pca_reduce_windows, rm_pca_reduce_windows_multi; rm_motion.hip):
+//   frame-parallel front   crops, uint8 pyrDown levels and Scharr derivatives of all frames of a chunk; the grid is (pixel block,
+//                          image of the chunk, subject), a workgroup beyond its subject's pixel or level count leaves at once
+//   point-parallel tracker one wavefront per (subject, point) walks the chunk's frames in order (lk_track_point, the per-frame body
+//                          of k_lk_track); its input for frame t is its own output for frame t - 1.  Waves never talk to each other,
+//                          and the tracks of different subjects are as independent as the tracks of different points.
+//   frame-parallel finish  one workgroup per (frame, subject): the float32 mean of old - new over the live points in point order
+//                          (flow_finish_wave, the body of k_flow_finish) and, for the clip's last frame, the survivors packed in
+//                          point order
+// Points keep their index through the whole clip (a lost point stays dead: the reference drops st == 0 points, base.py:377-382, and
+// the mean of base.py:388 runs over the survivors in point order, packed or not), so nothing is compacted between frames or chunks.
 // Only kernels live here.  Their arithmetic is the shared __device__ bodies of rm_flow.h / rm_kernels.h as they stand
 // (roi_to_u8_grid, pyr_down_u8_px, scharr_px, lk_track_point, flow_finish_wave, flow_finish_seq, pca_reduce_wave), which is why
-// subject k's numbers equal rm_flow_clip's on its own state bit for bit.
+// a subject's numbers equal rm_flow_step's on its own state bit for bit.
 #pragma once
 #include "rm_flow.h"
 
 namespace rm {
 
 // One row of the per-call subject table (device memory, uploaded with the per-point subject indices in one copy).  ROIs differ in
-// size, so they differ in level count, image sizes and point count.  L is the subject's LKLevels as k_lk_track_clip takes it: per
+// size, so they differ in level count, image sizes and point count.  L is the subject's LKLevels as lk_track_point takes it: per
 // level h, w, the distance between consecutive images of the chunk (stride), and the addresses of image 0 (prev), image 1 (next)
 // and the derivatives of image 0 -- the pooled arenas' bases plus the subject's offsets, added by the host.
 struct FlowSubject {
@@ -61,9 +66,13 @@ RM_KERNEL __launch_bounds__(256) void k_flow_multi_carry(const FlowSubject *__re
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < px; i += (size_t)gridDim.x * 256) img0[i] = img0[(size_t)n * px + i];
 }
 
-// k_lk_track_clip for the points of all subjects: workgroup p (one wave) is global point p, subject pt_subject[p].  The subject's
-// LKLevels is read from its table row with wave-uniform loads; start / start_alive / end / end_alive [P] and pos [nframes][P][2] /
-// status [nframes][P] are indexed by the global point index, so subject k's rows are k_lk_track_clip's arrays at offset S.pt0.
+// One wavefront per point over the `nframes` frames of a chunk: workgroup p (one wave) is global point p, subject pt_subject[p].
+// The subject's LKLevels, read from its table row with wave-uniform loads, describes image 0 (prev) and image 1 (next) of the chunk
+// with the distance between consecutive images per level (L.stride): frame t tracks from image t to image t + 1.
+// start / start_alive [P]: the point's position and whether it still lives when the chunk begins; pos [nframes][P][2] and
+// status [nframes][P]: what k_lk_track would have written frame after frame (status 0 for every frame behind the one that lost the
+// point: its wave leaves); end / end_alive [P]: what the next chunk starts from.  All are indexed by the global point index, so
+// subject k's rows lie at offset S.pt0.
 template <int ROUNDS>
 __global__ __launch_bounds__(64) void k_lk_track_multi_clip(const FlowSubject *__restrict__ tab, const int *__restrict__ pt_subject, int nframes,
                                                             const float *start, const uint8_t *start_alive, int npts_all, int win_w, int win_h,
@@ -94,9 +103,10 @@ __global__ __launch_bounds__(64) void k_lk_track_multi_clip(const FlowSubject *_
     if (lane == 0) { end[2 * p] = px; end[2 * p + 1] = py; end_alive[p] = (uint8_t)st; }
 }
 
-// frame t = blockIdx.x of the chunk, subject blockIdx.y: k_flow_finish_clip on the subject's slice of the point arrays;
-// res [nframes][nsub][4] = {mean_x, mean_y, n_good, -}.  pack: the chunk ends the clip, its last frame's survivors go to S.next_pts.
-// The two kernels share a grid; each leaves the subjects of the other kind alone (npts against FLOW_FINISH_MAX, as rm_flow_clip decides).
+// frame t = blockIdx.x of the chunk, subject blockIdx.y, on the subject's slice of the point arrays: old = the positions frame
+// t - 1 left (start for t == 0), new = pos[t]; res [nframes][nsub][4] = {mean_x, mean_y, n_good, -}.  pack: the chunk ends the
+// clip, its last frame's survivors go to S.next_pts.  The two kernels share a grid; each leaves the subjects of the other kind
+// alone (npts against FLOW_FINISH_MAX, as rm_flow_step decides: the second one walks global memory with one thread).
 RM_KERNEL __launch_bounds__(64) void k_flow_finish_multi(const FlowSubject *__restrict__ tab, const float *start, const float *pos, const uint8_t *status,
                                                          int npts_all, int nframes, float *res, int pack)
 {
@@ -121,8 +131,8 @@ RM_KERNEL void k_flow_finish_multi_seq(const FlowSubject *__restrict__ tab, cons
                     pack && t == nframes - 1 ? S.next_pts : nullptr);
 }
 
-// k_pca_reduce_windows over several motion lists in one launch: output b belongs to the list whose first row is map[2 b] and is
-// that list's row j = map[2 b + 1]; it reduces rows max(0, j + 1 - window) .. j of its own list
+// rm_pca_reduce of every window of several motion lists in one launch: output b belongs to the list whose first row is map[2 b]
+// and is that list's row j = map[2 b + 1]; workgroup b reduces rows max(0, j + 1 - window) .. j of its own list
 RM_KERNEL __launch_bounds__(64) void k_pca_reduce_windows_multi(const float *motion, const int *__restrict__ map, int window, double *out)
 {
     const int row0 = map[2 * blockIdx.x], j = map[2 * blockIdx.x + 1];

@@ -46,7 +46,6 @@
 #include "rm_xstore.h"
 #include "rm_ccl.h"
 #include "rm_flow.h"
-#include "rm_flow_clip.h"
 #include "rm_subjects.h"
 
 // sets the thread's error string (rm_last_error_string) and returns `code`
@@ -277,6 +276,16 @@ static inline unsigned nblk(size_t n, unsigned per, unsigned cap = 8192)
     return (unsigned)(b > cap ? cap : b);
 }
 static inline bool valid_dtype(int d) { return d == RM_U8 || d == RM_F16 || d == RM_F32 || d == RM_F64; }
+// f(T()) with T the element type of a frame dtype (valid_dtype): the one four-way switch behind the kernels templated on it
+template <typename F> static inline void dispatch_dtype(int dtype, F &&f)
+{
+    switch (dtype) {
+    case RM_U8: f(uint8_t()); break;
+    case RM_F16: f(__half()); break;
+    case RM_F32: f(float()); break;
+    default: f(double()); break;
+    }
+}
 // frame BUFFERS of the calibration entry points may also be RM_BGR8 ([T,H,W,3] uint8: base.py:230's cvtColor happens on the device)
 static inline bool valid_buffer_dtype(int d) { return valid_dtype(d) || d == RM_BGR8; }
 static inline int dtype_vec(int dtype) { return dtype == RM_F64 ? 2 : dtype == RM_F32 ? 4 : dtype == RM_F16 ? 8 : 16; }   // pixels per 16-byte aligned lane-load unit

@@ -2690,14 +2690,6 @@ __global__ __launch_bounds__(256) void k_roi_to_u8(const Tin *frame, int W, int 
     roi_to_u8_grid(frame, W, x, y, w, h, dst);
 }
 
-// ... and the crops of a clip's frames in one launch: blockIdx.y is the frame, the crops lie `dst_stride` bytes apart (rm_flow_clip)
-template <typename Tin>
-__global__ __launch_bounds__(256) void k_roi_to_u8_clip(const Tin *frames, size_t frame_px, int W, int x, int y, int w, int h, uint8_t *dst,
-                                                        size_t dst_stride)
-{
-    roi_to_u8_grid(frames + (size_t)blockIdx.y * frame_px, W, x, y, w, h, dst + (size_t)blockIdx.y * dst_stride);
-}
-
 // cv2.cvtColor(BGR2GRAY), base.py:230: Y = (B*1868 + G*9617 + R*4899 + 8192) >> 14
 RM_KERNEL __launch_bounds__(256) void k_bgr_to_gray(const uint8_t *bgr, size_t npix, uint8_t *gray)
 {

@@ -17,12 +17,10 @@ extern "C" int rm_roi_mean(rm_ctx *ctx, const void *frame, int dtype, int H, int
     hipStream_t s = (hipStream_t)stream;
     double *d = nullptr;
     RM_TRY(ws(ctx, "roi_mean", 1, &d));
-    switch (dtype) {
-    case RM_U8: hipLaunchKernelGGL((k_roi_mean<uint8_t>), dim3(1), dim3(256), 0, s, (const uint8_t *)frame, W, x, y, w, h, d); break;
-    case RM_F16: hipLaunchKernelGGL((k_roi_mean<__half>), dim3(1), dim3(256), 0, s, (const __half *)frame, W, x, y, w, h, d); break;
-    case RM_F32: hipLaunchKernelGGL((k_roi_mean<float>), dim3(1), dim3(256), 0, s, (const float *)frame, W, x, y, w, h, d); break;
-    default: hipLaunchKernelGGL((k_roi_mean<double>), dim3(1), dim3(256), 0, s, (const double *)frame, W, x, y, w, h, d); break;
-    }
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_roi_mean<T>), dim3(1), dim3(256), 0, s, (const T *)frame, W, x, y, w, h, d);
+    });
     LAUNCH_CHECK();
     HIP_TRY(hipMemcpyAsync(out, d, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(stream_wait(s));
@@ -35,12 +33,10 @@ extern "C" int rm_roi_to_uint8(rm_ctx *ctx, const void *frame, int dtype, int H,
     if (!ctx || !frame || !dst || !valid_dtype(dtype) || !roi_ok(H, W, x, y, w, h)) return fail(RM_E_BADARG, "rm_roi_to_uint8: bad argument");
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(nblk((size_t)w * h, 256, 1024)), block(256);
-    switch (dtype) {
-    case RM_U8: hipLaunchKernelGGL((k_roi_to_u8<uint8_t>), grid, block, 0, s, (const uint8_t *)frame, W, x, y, w, h, dst); break;
-    case RM_F16: hipLaunchKernelGGL((k_roi_to_u8<__half>), grid, block, 0, s, (const __half *)frame, W, x, y, w, h, dst); break;
-    case RM_F32: hipLaunchKernelGGL((k_roi_to_u8<float>), grid, block, 0, s, (const float *)frame, W, x, y, w, h, dst); break;
-    default: hipLaunchKernelGGL((k_roi_to_u8<double>), grid, block, 0, s, (const double *)frame, W, x, y, w, h, dst); break;
-    }
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_roi_to_u8<T>), grid, block, 0, s, (const T *)frame, W, x, y, w, h, dst);
+    });
     LAUNCH_CHECK();
     return RM_OK;
 }
@@ -123,22 +119,28 @@ extern "C" int rm_flow_state_destroy(rm_flow_state *st)
     return RM_OK;
 }
 
-static int flow_state_pts(FlowState &fs, float **pts_a, float **pts_b)
+// a named buffer of a flow workspace, or the workspace's error as the call's
+template <typename T> static int flow_buf(FlowWorkspace &ws, const std::string &name, size_t bytes, T **out)
 {
     std::string err;
-    int rc;
-    if ((rc = fs.ws.get("pts_a", sizeof(float) * 2 * (size_t)fs.cap, (void **)pts_a, err)) < 0) return fail(rc, "%s", err.c_str());
-    if ((rc = fs.ws.get("pts_b", sizeof(float) * 2 * (size_t)fs.cap, (void **)pts_b, err)) < 0) return fail(rc, "%s", err.c_str());
-    return RM_OK;
+    const int rc = ws.get(name, bytes, (void **)out, err);
+    return rc < 0 ? fail(rc, "%s", err.c_str()) : RM_OK;
 }
 
-static int flow_state_crop(FlowState &fs, int side, uint8_t **crop)
+static int flow_state_pts(FlowState &fs, float **pts_a, float **pts_b)
+{
+    RM_TRY(flow_buf(fs.ws, "pts_a", sizeof(float) * 2 * (size_t)fs.cap, pts_a));
+    return flow_buf(fs.ws, "pts_b", sizeof(float) * 2 * (size_t)fs.cap, pts_b);
+}
+
+// level `level` of the pyramid of one side of a state (level 0: the crop itself)
+static int flow_state_pyr(FlowState &fs, int side, int level, size_t bytes, uint8_t **out)
 {
     std::string err;
-    const int rc = flow_side_buf(fs, side, "pyr", 0, (size_t)fs.w * fs.h, (void **)crop, err);
-    if (rc < 0) return fail(rc, "%s", err.c_str());
-    return RM_OK;
+    const int rc = flow_side_buf(fs, side, "pyr", level, bytes, (void **)out, err);
+    return rc < 0 ? fail(rc, "%s", err.c_str()) : RM_OK;
 }
+static int flow_state_crop(FlowState &fs, int side, uint8_t **crop) { return flow_state_pyr(fs, side, 0, (size_t)fs.w * fs.h, crop); }
 
 extern "C" int rm_flow_begin(rm_ctx *ctx, rm_flow_state *state, const void *frame, int dtype, int H, int W, int x, int y, int w, int h, int max_corners,
                              double quality, double min_distance, int block_size, float *pts_host, int *n_host, void *stream)
@@ -196,10 +198,9 @@ extern "C" int rm_flow_step(rm_ctx *ctx, rm_flow_state *state, const void *frame
     if (npts > 0) {
         std::string err;
         float *d_out = nullptr; uint8_t *d_st = nullptr; float *dev_res = nullptr;
-        int rc;
-        if ((rc = fs.ws.get("lk_pts_out", sizeof(float) * 2 * (size_t)npts, (void **)&d_out, err)) < 0) return fail(rc, "%s", err.c_str());
-        if ((rc = fs.ws.get("lk_status", (size_t)npts, (void **)&d_st, err)) < 0) return fail(rc, "%s", err.c_str());
-        rc = flow_track_resident(fs, prev_side, cur_side, pts, npts, win_w, win_h, max_level, max_count, epsilon, d_out, d_st, s, err);
+        RM_TRY(flow_buf(fs.ws, "lk_pts_out", sizeof(float) * 2 * (size_t)npts, &d_out));
+        RM_TRY(flow_buf(fs.ws, "lk_status", (size_t)npts, &d_st));
+        const int rc = flow_track_resident(fs, prev_side, cur_side, pts, npts, win_w, win_h, max_level, max_count, epsilon, d_out, d_st, s, err);
         if (rc < 0) return fail(rc, "%s", err.c_str());
         HIP_TRY(hipHostGetDevicePointer((void **)&dev_res, fs.res, 0));
         if (npts <= FLOW_FINISH_MAX) hipLaunchKernelGGL(k_flow_finish<>, dim3(1), dim3(64), 2 * sizeof(float) * (size_t)flow_finish_pitch(npts), s, pts, d_out, d_st, npts, dev_res, pts_next);
@@ -240,12 +241,10 @@ extern "C" int rm_roi_mean_clip(rm_ctx *ctx, const void *frames, int dtype, int 
     double *d = nullptr;
     RM_TRY(ws(ctx, "roi_mean_clip", (size_t)N, &d));
     const size_t px = (size_t)H * W;
-    switch (dtype) {
-    case RM_U8: hipLaunchKernelGGL((k_roi_mean_clip<uint8_t>), dim3(N), dim3(256), 0, s, (const uint8_t *)frames, px, W, x, y, w, h, d); break;
-    case RM_F16: hipLaunchKernelGGL((k_roi_mean_clip<__half>), dim3(N), dim3(256), 0, s, (const __half *)frames, px, W, x, y, w, h, d); break;
-    case RM_F32: hipLaunchKernelGGL((k_roi_mean_clip<float>), dim3(N), dim3(256), 0, s, (const float *)frames, px, W, x, y, w, h, d); break;
-    default: hipLaunchKernelGGL((k_roi_mean_clip<double>), dim3(N), dim3(256), 0, s, (const double *)frames, px, W, x, y, w, h, d); break;
-    }
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_roi_mean_clip<T>), dim3(N), dim3(256), 0, s, (const T *)frames, px, W, x, y, w, h, d);
+    });
     LAUNCH_CHECK();
     HIP_TRY(hipMemcpyAsync(out, d, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
     HIP_TRY(stream_wait(s));
@@ -272,229 +271,55 @@ extern "C" int rm_roi_mean_multi_clip(rm_ctx *ctx, const void *frames, int dtype
     HIP_TRY(hipMemcpyAsync(d_rois, rois, sizeof(int32_t) * 4 * (size_t)K, hipMemcpyHostToDevice, s));
     const size_t px = (size_t)H * W;
     const dim3 grid((unsigned)(N * K)), block(256);
-    switch (dtype) {
-    case RM_U8: hipLaunchKernelGGL((k_roi_mean_multi_clip<uint8_t>), grid, block, 0, s, (const uint8_t *)frames, px, W, (const int *)d_rois, K, d); break;
-    case RM_F16: hipLaunchKernelGGL((k_roi_mean_multi_clip<__half>), grid, block, 0, s, (const __half *)frames, px, W, (const int *)d_rois, K, d); break;
-    case RM_F32: hipLaunchKernelGGL((k_roi_mean_multi_clip<float>), grid, block, 0, s, (const float *)frames, px, W, (const int *)d_rois, K, d); break;
-    default: hipLaunchKernelGGL((k_roi_mean_multi_clip<double>), grid, block, 0, s, (const double *)frames, px, W, (const int *)d_rois, K, d); break;
-    }
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_roi_mean_multi_clip<T>), grid, block, 0, s, (const T *)frames, px, W, (const int *)d_rois, K, d);
+    });
     LAUNCH_CHECK();
     HIP_TRY(hipMemcpyAsync(out, d, sizeof(double) * (size_t)N * K, hipMemcpyDeviceToHost, s));
     HIP_TRY(stream_wait(s));   // (the rectangles' host memory is the caller's again as well)
     return RM_OK;
 }
 
-extern "C" int rm_pca_reduce_windows(rm_ctx *ctx, const float *motion, int n, int first, int window, double *out, void *stream)
-{
-    if (!ctx || !motion || !out || n < 0 || first < 0 || first > n || window < 1) return fail(RM_E_BADARG, "rm_pca_reduce_windows: bad argument");
-    if (first == n) return RM_OK;
-    hipStream_t s = (hipStream_t)stream;
-    std::string err;
-    float *d_m = nullptr;
-    double *d_o = nullptr;
-    int rc;
-    if ((rc = ctx->flow.get("pcaw_in", sizeof(float) * 2 * (size_t)n, (void **)&d_m, err)) < 0) return fail(rc, "%s", err.c_str());
-    if ((rc = ctx->flow.get("pcaw_out", sizeof(double) * (size_t)(n - first), (void **)&d_o, err)) < 0) return fail(rc, "%s", err.c_str());
-    HIP_TRY(hipMemcpyAsync(d_m, motion, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_pca_reduce_windows<>, dim3(n - first), dim3(64), 0, s, d_m, first, window, d_o);
-    LAUNCH_CHECK();
-    HIP_TRY(hipMemcpyAsync(out, d_o, sizeof(double) * (size_t)(n - first), hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
-    return RM_OK;
-}
-
-// the crops of `n` frames of a clip, `dst_stride` bytes apart, in one launch
-static int flow_crop_clip(const void *frames, int dtype, int n, int H, int W, int x, int y, int w, int h, uint8_t *dst, size_t dst_stride, hipStream_t s)
-{
-    const size_t px = (size_t)H * W;
-    dim3 grid(nblk((size_t)w * h, 256, 1024), n), block(256);
-    switch (dtype) {
-    case RM_U8: hipLaunchKernelGGL((k_roi_to_u8_clip<uint8_t>), grid, block, 0, s, (const uint8_t *)frames, px, W, x, y, w, h, dst, dst_stride); break;
-    case RM_F16: hipLaunchKernelGGL((k_roi_to_u8_clip<__half>), grid, block, 0, s, (const __half *)frames, px, W, x, y, w, h, dst, dst_stride); break;
-    case RM_F32: hipLaunchKernelGGL((k_roi_to_u8_clip<float>), grid, block, 0, s, (const float *)frames, px, W, x, y, w, h, dst, dst_stride); break;
-    default: hipLaunchKernelGGL((k_roi_to_u8_clip<double>), grid, block, 0, s, (const double *)frames, px, W, x, y, w, h, dst, dst_stride); break;
-    }
-    LAUNCH_CHECK();
-    return RM_OK;
-}
-
+// ------------------------------------------------------------------------------------------
+// optical flow and windowed PCA over a clip (rm_flow_multi.h): one path for K subjects, the one-subject entry points are its K == 1
+// ------------------------------------------------------------------------------------------
 constexpr long long FLOW_CLIP_BYTES = 256ll << 20;   // workspace cap of one chunk's crops, pyramids and derivatives (rm_debug_set flow_clip_bytes)
 constexpr int FLOW_CLIP_MAX_CHUNK = 32768;           // frames per chunk at most: the image index is a grid's y dimension
 
-// N successive rm_flow_step calls as one: see rm_flow_clip.h for the shape of the device work.  The clip is worked through in chunks
-// of C frames whose images (the chunk's frames behind image 0, the crop the chunk tracks from) share one workspace; a point keeps its
-// index through all chunks, its position and life going from one chunk's tracker to the next through `carry`.
-extern "C" int rm_flow_clip(rm_ctx *ctx, rm_flow_state *state, const void *frames, int dtype, int N, int H, int W, int x, int y, int w, int h,
-                            int win_w, int win_h, int max_level, int max_count, double epsilon, float *mean_xy_host, int *n_good_host, void *stream)
-{
-    if (!ctx || !state || !frames || !mean_xy_host || !n_good_host || N < 1 || !valid_dtype(dtype) || !roi_ok(H, W, x, y, w, h) || win_w < 3 ||
-        win_h < 3 || max_level < 0)
-        return fail(RM_E_BADARG, "rm_flow_clip: bad argument");
-    FlowState &fs = state->fs;
-    if (!fs.begun || w != fs.w || h != fs.h) return fail(RM_E_BADARG, "rm_flow_clip: rm_flow_begin has not been called on this state for this ROI size");
-    if (state->device != ctx->device) return fail(RM_E_BADARG, "rm_flow_clip: the flow state belongs to another device");
-    const int npts = fs.npts;
-    if (npts > 0) {   // (rm_flow_step meets these limits in its tracking stage, which a state without points never reaches)
-        if (win_w * win_h > LK_MAX_WIN) return fail(RM_E_UNSUPPORTED, "winSize too large");
-        if (lk_max_level(h, w, win_w, win_h, max_level) + 1 > LK_MAX_LEVELS) return fail(RM_E_UNSUPPORTED, "too many pyramid levels");
-    }
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t frame_bytes = (size_t)H * W * dtype_size(dtype);
-    const int prev_side = fs.flip, cur_side = fs.flip ^ 1;
-    uint8_t *prev = nullptr, *cur = nullptr; float *pa = nullptr, *pb = nullptr;
-    RM_TRY(flow_state_crop(fs, prev_side, &prev));
-    RM_TRY(flow_state_crop(fs, cur_side, &cur));
-    RM_TRY(flow_state_pts(fs, &pa, &pb));
-    for (int i = 0; i < N; ++i) { mean_xy_host[2 * i] = mean_xy_host[2 * i + 1] = 0.f; n_good_host[i] = 0; }
-    if (npts == 0) {   // nothing to track: the previous image advances to the clip's last frame (base.py:381)
-        RM_TRY(flow_crop(ctx, (const char *)frames + (size_t)(N - 1) * frame_bytes, dtype, H, W, x, y, w, h, cur, s));
-        fs.pyr_levels[cur_side] = 0; fs.deriv_levels[cur_side] = -1;
-        fs.flip ^= 1;
-        return RM_OK;
-    }
-    if (max_count < 0) max_count = 0;
-    if (max_count > 100) max_count = 100;
-    if (epsilon < 0) epsilon = 0;
-    if (epsilon > 10) epsilon = 10;
-    epsilon *= epsilon;
-    max_level = lk_max_level(h, w, win_w, win_h, max_level);
-    LKLevels L = {};
-    L.n = max_level + 1;
-    size_t slot_bytes = 0;
-    for (int l = 0, sh = h, sw = w; l <= max_level; ++l, sh = (sh + 1) / 2, sw = (sw + 1) / 2) {
-        L.h[l] = sh; L.w[l] = sw; L.stride[l] = (size_t)sh * sw;
-        slot_bytes += L.stride[l] * (1 + 2 * sizeof(short));
-    }
-    const long long cap = ctx->dbg.flow_clip_bytes > 0 ? ctx->dbg.flow_clip_bytes : FLOW_CLIP_BYTES;
-    const int C = (int)std::max<long long>(1, std::min<long long>(std::min(N, FLOW_CLIP_MAX_CHUNK), cap / (long long)slot_bytes - 1));
-    std::string err;
-    int rc;
-    uint8_t *img[LK_MAX_LEVELS]; short *der[LK_MAX_LEVELS];
-    for (int l = 0; l <= max_level; ++l) {
-        if ((rc = fs.ws.get("clip_img" + std::to_string(l), L.stride[l] * (size_t)(C + 1), (void **)&img[l], err)) < 0) return fail(rc, "%s", err.c_str());
-        if ((rc = fs.ws.get("clip_deriv" + std::to_string(l), L.stride[l] * 2 * sizeof(short) * (size_t)C, (void **)&der[l], err)) < 0) return fail(rc, "%s", err.c_str());
-        L.prev[l] = img[l]; L.next[l] = img[l] + L.stride[l]; L.deriv[l] = der[l];
-    }
-    float *d_pos = nullptr, *d_res = nullptr, *carry_p[2] = {nullptr, nullptr}; uint8_t *d_st = nullptr, *carry_a[2] = {nullptr, nullptr};
-    if ((rc = fs.ws.get("clip_pos", sizeof(float) * 2 * (size_t)npts * C, (void **)&d_pos, err)) < 0) return fail(rc, "%s", err.c_str());
-    if ((rc = fs.ws.get("clip_status", (size_t)npts * C, (void **)&d_st, err)) < 0) return fail(rc, "%s", err.c_str());
-    if ((rc = fs.ws.get("clip_res", sizeof(float) * 4 * (size_t)N, (void **)&d_res, err)) < 0) return fail(rc, "%s", err.c_str());
-    for (int k = 0; k < 2; ++k) {
-        if ((rc = fs.ws.get(k ? "clip_carry_pts_b" : "clip_carry_pts_a", sizeof(float) * 2 * (size_t)npts, (void **)&carry_p[k], err)) < 0) return fail(rc, "%s", err.c_str());
-        if ((rc = fs.ws.get(k ? "clip_carry_alive_b" : "clip_carry_alive_a", (size_t)npts, (void **)&carry_a[k], err)) < 0) return fail(rc, "%s", err.c_str());
-    }
-    float *pts = fs.flip ? pb : pa, *pts_next = fs.flip ? pa : pb;
-    HIP_TRY(hipMemcpyAsync(carry_p[0], pts, sizeof(float) * 2 * (size_t)npts, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemsetAsync(carry_a[0], 1, (size_t)npts, s));
-    HIP_TRY(hipMemcpyAsync(img[0], prev, L.stride[0], hipMemcpyDeviceToDevice, s));
-    int last = 0;   // the image of the chunk just done that holds its last frame
-    for (int c0 = 0, k = 0; c0 < N; c0 += C, ++k) {
-        const int n = std::min(C, N - c0);
-        const bool final_chunk = c0 + n == N;
-        // frame-parallel front: crops into images 1 .. n, the pyramids of images 0 .. n, the derivatives of images 0 .. n - 1
-        RM_TRY(flow_crop_clip((const char *)frames + (size_t)c0 * frame_bytes, dtype, n, H, W, x, y, w, h, img[0] + L.stride[0], L.stride[0], s));
-        for (int l = 1; l <= max_level; ++l)
-            hipLaunchKernelGGL(k_pyr_down_u8_clip<>, dim3((unsigned)((L.stride[l] + 255) / 256), n + 1), dim3(256), 0, s, img[l - 1], L.stride[l - 1],
-                               L.h[l - 1], L.w[l - 1], img[l], L.stride[l], L.h[l], L.w[l]);
-        for (int l = 0; l <= max_level; ++l)
-            hipLaunchKernelGGL(k_scharr_clip<>, dim3((unsigned)((L.stride[l] + 255) / 256), n), dim3(256), 0, s, img[l], L.stride[l], L.h[l], L.w[l], der[l]);
-        // point-parallel tracker, frame-parallel finish
-        const float *start = carry_p[k & 1]; const uint8_t *start_alive = carry_a[k & 1];
-        if (win_w * win_h <= 256)
-            hipLaunchKernelGGL(k_lk_track_clip<4>, dim3(npts), dim3(64), 0, s, L, n, start, start_alive, npts, win_w, win_h, max_count, epsilon, d_pos, d_st,
-                               carry_p[(k + 1) & 1], carry_a[(k + 1) & 1]);
-        else
-            hipLaunchKernelGGL(k_lk_track_clip<16>, dim3(npts), dim3(64), 0, s, L, n, start, start_alive, npts, win_w, win_h, max_count, epsilon, d_pos, d_st,
-                               carry_p[(k + 1) & 1], carry_a[(k + 1) & 1]);
-        float *next_pts = final_chunk ? pts_next : nullptr;
-        if (npts <= FLOW_FINISH_MAX)
-            hipLaunchKernelGGL(k_flow_finish_clip<>, dim3(n), dim3(64), 2 * sizeof(float) * (size_t)flow_finish_pitch(npts), s, start, d_pos, d_st, npts, n,
-                               d_res + 4 * (size_t)c0, next_pts);
-        else
-            hipLaunchKernelGGL(k_flow_finish_clip_seq<>, dim3(n), dim3(1), 0, s, start, d_pos, d_st, npts, n, d_res + 4 * (size_t)c0, next_pts);
-        LAUNCH_CHECK();
-        last = n;
-        if (!final_chunk) HIP_TRY(hipMemcpyAsync(img[0], img[0] + (size_t)n * L.stride[0], L.stride[0], hipMemcpyDeviceToDevice, s));
-    }
-    // the state the next call starts from: the last crop with its pyramid (derivatives are built by the call that tracks from it)
-    for (int l = 0; l <= max_level; ++l) {
-        uint8_t *dst = nullptr;
-        if ((rc = flow_side_buf(fs, cur_side, "pyr", l, L.stride[l], (void **)&dst, err)) < 0) return fail(rc, "%s", err.c_str());
-        HIP_TRY(hipMemcpyAsync(dst, img[l] + (size_t)last * L.stride[l], L.stride[l], hipMemcpyDeviceToDevice, s));
-    }
-    std::vector<float> res(4 * (size_t)N);
-    HIP_TRY(hipMemcpyAsync(res.data(), d_res, sizeof(float) * 4 * (size_t)N, hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
-    for (int i = 0; i < N; ++i) { mean_xy_host[2 * i] = res[4 * i]; mean_xy_host[2 * i + 1] = res[4 * i + 1]; n_good_host[i] = (int)res[4 * i + 2]; }
-    fs.pyr_levels[cur_side] = max_level; fs.deriv_levels[cur_side] = -1;
-    fs.npts = n_good_host[N - 1];
-    fs.flip ^= 1;
-    return RM_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// several subjects per clip (rm_flow_multi.h): K rm_flow_clip calls, K rm_pca_reduce_windows calls as one call each
-// ------------------------------------------------------------------------------------------
-template <typename Tin>
-static void launch_multi_crop(const void *frames, size_t px, int W, const FlowSubject *tab, dim3 grid, hipStream_t s)
-{
-    hipLaunchKernelGGL((k_flow_multi_crop<Tin>), grid, dim3(256), 0, s, (const Tin *)frames, px, W, tab);
-}
 static int flow_multi_crop(const void *frames, int dtype, int n, int H, int W, const FlowSubject *tab, int nsub, size_t max_px, hipStream_t s)
 {
     const size_t px = (size_t)H * W;
     const dim3 grid(nblk(max_px, 256, 1024), (unsigned)n, (unsigned)nsub);
-    switch (dtype) {
-    case RM_U8: launch_multi_crop<uint8_t>(frames, px, W, tab, grid, s); break;
-    case RM_F16: launch_multi_crop<__half>(frames, px, W, tab, grid, s); break;
-    case RM_F32: launch_multi_crop<float>(frames, px, W, tab, grid, s); break;
-    default: launch_multi_crop<double>(frames, px, W, tab, grid, s); break;
-    }
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_flow_multi_crop<T>), grid, dim3(256), 0, s, (const T *)frames, px, W, tab);
+    });
     LAUNCH_CHECK();
     return RM_OK;
 }
 
-// Subject k on states[k] with rectangle k, exactly as K rm_flow_clip calls would leave outputs and states.  The subjects that still
-// have points ("live") share the chunks of one clip walk: one chunk length C for all, their images and derivatives in two arenas of
-// the context, their points side by side under one global index (pt0 = prefix sum), so position and life pass from chunk to chunk
-// through carry buffers of the whole call.  A subject without points only gets the crop of the clip's last frame (one extra launch
-// for all of them).  Launches per chunk: 1 crop + (levels - 1) pyrDown + levels Scharr + 1 tracker + 1 or 2 finish (+ 1 carry).
-extern "C" int rm_flow_multi_clip(rm_ctx *ctx, rm_flow_state *const *states, const void *frames, int dtype, int N, int H, int W, const int32_t *rois,
-                                  int K, int win_w, int win_h, int max_level, int max_count, double epsilon, float *mean_xy_host,
-                                  int32_t *n_good_host, void *stream)
+// N successive rm_flow_step calls per subject as one call, subject k on states[k] with rectangle k.  The entry point has checked the
+// arguments; `who` is its name for the UNSUPPORTED texts, which then name the subject as well, or NULL for the one-subject entry,
+// whose texts are rm_flow_step's and name neither.  The clip is worked through in chunks of C frames.  The subjects that still have
+// points ("live") share the chunks of one clip walk: one chunk length C for all, their images (the chunk's frames behind image 0, the
+// crop the chunk tracks from) and derivatives in two arenas of the context, their points side by side under one global index (pt0 =
+// prefix sum); a point keeps its index through all chunks, its position and life going from one chunk's tracker to the next through
+// carry buffers of the whole call.  A subject without points only gets the crop of the clip's last frame (one extra launch for all
+// of them).  Launches per chunk: 1 crop + (levels - 1) pyrDown + levels Scharr + 1 tracker + 1 or 2 finish (+ 1 carry).
+static int flow_clips(rm_ctx *ctx, const char *who, rm_flow_state *const *states, const void *frames, int dtype, int N, int H, int W, const int32_t *rois,
+                      int K, int win_w, int win_h, int max_level, int max_count, double epsilon, float *mean_xy_host, int32_t *n_good_host, hipStream_t s)
 {
-    if (!ctx || !states || !frames || !rois || !mean_xy_host || !n_good_host || N < 1 || H < 1 || W < 1 || K < 1 || K > RM_MAX_ROIS ||
-        !valid_dtype(dtype) || win_w < 3 || win_h < 3 || max_level < 0 || (long long)N * K > 0x7fffffffll)
-        return fail(RM_E_BADARG, "rm_flow_multi_clip: bad argument (1 <= K <= %d)", RM_MAX_ROIS);
-    // the whole call is refused before anything is enqueued or any state is touched: argument errors of every subject first ...
-    for (int k = 0; k < K; ++k) {
-        const int32_t *r = rois + 4 * k;
-        if (!states[k]) return fail(RM_E_BADARG, "rm_flow_multi_clip: subject %d has no flow state (NULL)", k);
-        if (!roi_ok(H, W, r[0], r[1], r[2], r[3]))
-            return fail(RM_E_BADARG, "rm_flow_multi_clip: rectangle %d (%d, %d, %d, %d) does not lie inside the %d x %d frame", k, r[0], r[1], r[2], r[3], W, H);
-        const FlowState &fs = states[k]->fs;
-        if (!fs.begun || r[2] != fs.w || r[3] != fs.h)
-            return fail(RM_E_BADARG, "rm_flow_multi_clip: rm_flow_begin has not been called on the state of subject %d for this ROI size", k);
-        if (states[k]->device != ctx->device) return fail(RM_E_BADARG, "rm_flow_multi_clip: the flow state of subject %d belongs to another device", k);
-        for (int j = 0; j < k; ++j)
-            if (states[j] == states[k]) return fail(RM_E_BADARG, "rm_flow_multi_clip: subject %d uses the flow state of subject %d", k, j);
-    }
-    // ... then the limits rm_flow_clip meets for a subject that still has points
+    // the limits rm_flow_step meets in its tracking stage, which a state without points never reaches: still nothing is enqueued
     for (int k = 0; k < K; ++k) {
         if (states[k]->fs.npts == 0) continue;
-        if (win_w * win_h > LK_MAX_WIN) return fail(RM_E_UNSUPPORTED, "rm_flow_multi_clip: winSize too large (subject %d)", k);
-        if (lk_max_level(rois[4 * k + 3], rois[4 * k + 2], win_w, win_h, max_level) + 1 > LK_MAX_LEVELS)
-            return fail(RM_E_UNSUPPORTED, "rm_flow_multi_clip: too many pyramid levels (subject %d)", k);
+        const char *what = win_w * win_h > LK_MAX_WIN ? "winSize too large"
+                         : lk_max_level(rois[4 * k + 3], rois[4 * k + 2], win_w, win_h, max_level) + 1 > LK_MAX_LEVELS ? "too many pyramid levels" : nullptr;
+        if (what) return who ? fail(RM_E_UNSUPPORTED, "%s: %s (subject %d)", who, what, k) : fail(RM_E_UNSUPPORTED, "%s", what);
     }
-    hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t frame_bytes = (size_t)H * W * dtype_size(dtype);
-    if (max_count < 0) max_count = 0;
-    if (max_count > 100) max_count = 100;
-    if (epsilon < 0) epsilon = 0;
-    if (epsilon > 10) epsilon = 10;
-    epsilon *= epsilon;
+    lk_clamp_criteria(max_count, epsilon);
 
     // table rows: the live subjects first (row j = subject live[j]), then the others
     std::vector<int> live, dead;
@@ -530,26 +355,24 @@ extern "C" int rm_flow_multi_clip(rm_ctx *ctx, rm_flow_state *const *states, con
     const int C = KL ? (int)std::max<long long>(1, std::min<long long>(std::min(N, FLOW_CLIP_MAX_CHUNK), cap / (long long)slot_bytes - 1)) : 1;
 
     // every buffer the call needs, of the context (arenas, point arrays, table) and of the states, before anything is enqueued
-    std::string err;
-    int rc;
     uint8_t *img_arena = nullptr, *d_st = nullptr, *carry_a[2] = {nullptr, nullptr}, *d_tab_bytes = nullptr;
     short *der_arena = nullptr;
     float *d_pos = nullptr, *d_res = nullptr, *carry_p[2] = {nullptr, nullptr};
     const size_t tab_bytes = sizeof(FlowSubject) * (size_t)K, up_bytes = tab_bytes + sizeof(int) * (size_t)P;
-    if ((rc = ctx->flow.get("fm_table", up_bytes, (void **)&d_tab_bytes, err)) < 0) return fail(rc, "%s", err.c_str());
+    RM_TRY(flow_buf(ctx->flow, "fm_table", up_bytes, &d_tab_bytes));
     const FlowSubject *d_tab = (const FlowSubject *)d_tab_bytes;
     const int *d_pt_subject = (const int *)(d_tab_bytes + tab_bytes);
     if (KL) {
         size_t img_px = 0;   // pixels of one image of every level of every live subject
         for (int j = 0; j < KL; ++j) for (int l = 0; l < tab[j].L.n; ++l) img_px += tab[j].L.stride[l];
-        if ((rc = ctx->flow.get("fm_img", img_px * (size_t)(C + 1), (void **)&img_arena, err)) < 0) return fail(rc, "%s", err.c_str());
-        if ((rc = ctx->flow.get("fm_deriv", img_px * 2 * sizeof(short) * (size_t)C, (void **)&der_arena, err)) < 0) return fail(rc, "%s", err.c_str());
-        if ((rc = ctx->flow.get("fm_pos", sizeof(float) * 2 * (size_t)P * C, (void **)&d_pos, err)) < 0) return fail(rc, "%s", err.c_str());
-        if ((rc = ctx->flow.get("fm_status", (size_t)P * C, (void **)&d_st, err)) < 0) return fail(rc, "%s", err.c_str());
-        if ((rc = ctx->flow.get("fm_res", sizeof(float) * 4 * (size_t)N * KL, (void **)&d_res, err)) < 0) return fail(rc, "%s", err.c_str());
+        RM_TRY(flow_buf(ctx->flow, "fm_img", img_px * (size_t)(C + 1), &img_arena));
+        RM_TRY(flow_buf(ctx->flow, "fm_deriv", img_px * 2 * sizeof(short) * (size_t)C, &der_arena));
+        RM_TRY(flow_buf(ctx->flow, "fm_pos", sizeof(float) * 2 * (size_t)P * C, &d_pos));
+        RM_TRY(flow_buf(ctx->flow, "fm_status", (size_t)P * C, &d_st));
+        RM_TRY(flow_buf(ctx->flow, "fm_res", sizeof(float) * 4 * (size_t)N * KL, &d_res));
         for (int i = 0; i < 2; ++i) {
-            if ((rc = ctx->flow.get(i ? "fm_carry_pts_b" : "fm_carry_pts_a", sizeof(float) * 2 * (size_t)P, (void **)&carry_p[i], err)) < 0) return fail(rc, "%s", err.c_str());
-            if ((rc = ctx->flow.get(i ? "fm_carry_alive_b" : "fm_carry_alive_a", (size_t)P, (void **)&carry_a[i], err)) < 0) return fail(rc, "%s", err.c_str());
+            RM_TRY(flow_buf(ctx->flow, i ? "fm_carry_pts_b" : "fm_carry_pts_a", sizeof(float) * 2 * (size_t)P, &carry_p[i]));
+            RM_TRY(flow_buf(ctx->flow, i ? "fm_carry_alive_b" : "fm_carry_alive_a", (size_t)P, &carry_a[i]));
         }
     }
     std::vector<uint8_t *> st_prev((size_t)K, nullptr);                  // [k]: the crop the subject tracks from
@@ -569,8 +392,7 @@ extern "C" int rm_flow_multi_clip(rm_ctx *ctx, rm_flow_state *const *states, con
         st_pts[k] = fs.flip ? pb : pa;
         S.next_pts = fs.flip ? pa : pb;
         for (int l = 0; l < S.L.n; ++l) {
-            if (l > 0 && (rc = flow_side_buf(fs, cur_side, "pyr", l, S.L.stride[l], (void **)&st_cur[(size_t)k * LK_MAX_LEVELS + l], err)) < 0)
-                return fail(rc, "%s", err.c_str());
+            if (l > 0) RM_TRY(flow_state_pyr(fs, cur_side, l, S.L.stride[l], &st_cur[(size_t)k * LK_MAX_LEVELS + l]));
             S.L.prev[l] = img_arena + img_off; S.L.next[l] = S.L.prev[l] + S.L.stride[l]; S.L.deriv[l] = der_arena + der_off;
             img_off += S.L.stride[l] * (size_t)(C + 1); der_off += S.L.stride[l] * 2 * (size_t)C;
         }
@@ -651,6 +473,77 @@ extern "C" int rm_flow_multi_clip(rm_ctx *ctx, rm_flow_state *const *states, con
     return RM_OK;
 }
 
+// the one-subject entry: its own argument check, then the driver with K = 1 (its outputs [N][1][2] and [N][1] are this call's layout)
+extern "C" int rm_flow_clip(rm_ctx *ctx, rm_flow_state *state, const void *frames, int dtype, int N, int H, int W, int x, int y, int w, int h,
+                            int win_w, int win_h, int max_level, int max_count, double epsilon, float *mean_xy_host, int *n_good_host, void *stream)
+{
+    if (!ctx || !state || !frames || !mean_xy_host || !n_good_host || N < 1 || !valid_dtype(dtype) || !roi_ok(H, W, x, y, w, h) || win_w < 3 ||
+        win_h < 3 || max_level < 0)
+        return fail(RM_E_BADARG, "rm_flow_clip: bad argument");
+    const FlowState &fs = state->fs;
+    if (!fs.begun || w != fs.w || h != fs.h) return fail(RM_E_BADARG, "rm_flow_clip: rm_flow_begin has not been called on this state for this ROI size");
+    if (state->device != ctx->device) return fail(RM_E_BADARG, "rm_flow_clip: the flow state belongs to another device");
+    const int32_t roi[4] = {x, y, w, h};
+    return flow_clips(ctx, nullptr, &state, frames, dtype, N, H, W, roi, 1, win_w, win_h, max_level, max_count, epsilon, mean_xy_host, n_good_host,
+                      (hipStream_t)stream);
+}
+
+extern "C" int rm_flow_multi_clip(rm_ctx *ctx, rm_flow_state *const *states, const void *frames, int dtype, int N, int H, int W, const int32_t *rois,
+                                  int K, int win_w, int win_h, int max_level, int max_count, double epsilon, float *mean_xy_host,
+                                  int32_t *n_good_host, void *stream)
+{
+    if (!ctx || !states || !frames || !rois || !mean_xy_host || !n_good_host || N < 1 || H < 1 || W < 1 || K < 1 || K > RM_MAX_ROIS ||
+        !valid_dtype(dtype) || win_w < 3 || win_h < 3 || max_level < 0 || (long long)N * K > 0x7fffffffll)
+        return fail(RM_E_BADARG, "rm_flow_multi_clip: bad argument (1 <= K <= %d)", RM_MAX_ROIS);
+    // the whole call is refused before anything is enqueued or any state is touched: the argument errors of every subject come first
+    for (int k = 0; k < K; ++k) {
+        const int32_t *r = rois + 4 * k;
+        if (!states[k]) return fail(RM_E_BADARG, "rm_flow_multi_clip: subject %d has no flow state (NULL)", k);
+        if (!roi_ok(H, W, r[0], r[1], r[2], r[3]))
+            return fail(RM_E_BADARG, "rm_flow_multi_clip: rectangle %d (%d, %d, %d, %d) does not lie inside the %d x %d frame", k, r[0], r[1], r[2], r[3], W, H);
+        const FlowState &fs = states[k]->fs;
+        if (!fs.begun || r[2] != fs.w || r[3] != fs.h)
+            return fail(RM_E_BADARG, "rm_flow_multi_clip: rm_flow_begin has not been called on the state of subject %d for this ROI size", k);
+        if (states[k]->device != ctx->device) return fail(RM_E_BADARG, "rm_flow_multi_clip: the flow state of subject %d belongs to another device", k);
+        for (int j = 0; j < k; ++j)
+            if (states[j] == states[k]) return fail(RM_E_BADARG, "rm_flow_multi_clip: subject %d uses the flow state of subject %d", k, j);
+    }
+    return flow_clips(ctx, "rm_flow_multi_clip", states, frames, dtype, N, H, W, rois, K, win_w, win_h, max_level, max_count, epsilon, mean_xy_host,
+                      n_good_host, (hipStream_t)stream);
+}
+
+// The windows of K motion lists in one upload, one launch, one download and one wait (the entry points have checked the segments):
+// `rows` rows of motion are in use, `nout` > 0 values come back.
+static int pca_windows(rm_ctx *ctx, const float *motion, const int32_t *seg, int K, int window, long long rows, long long nout, double *out, hipStream_t s)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    // one upload: the rows, behind them the (first row of the list, row inside the list) pair of every output
+    const size_t rows_bytes = (sizeof(float) * 2 * (size_t)rows + 7) / 8 * 8, map_bytes = sizeof(int) * 2 * (size_t)nout;
+    std::vector<uint8_t> up(rows_bytes + map_bytes);
+    std::memcpy(up.data(), motion, sizeof(float) * 2 * (size_t)rows);
+    int *map = (int *)(up.data() + rows_bytes);
+    for (int k = 0; k < K; ++k)
+        for (int j = seg[3 * k + 2]; j < seg[3 * k + 1]; ++j) { *map++ = seg[3 * k]; *map++ = j; }
+    uint8_t *d_in = nullptr;
+    double *d_o = nullptr;
+    RM_TRY(flow_buf(ctx->flow, "pcawm_in", up.size(), &d_in));
+    RM_TRY(flow_buf(ctx->flow, "pcawm_out", sizeof(double) * (size_t)nout, &d_o));
+    HIP_TRY(hipMemcpyAsync(d_in, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_pca_reduce_windows_multi<>, dim3((unsigned)nout), dim3(64), 0, s, (const float *)d_in, (const int *)(d_in + rows_bytes), window, d_o);
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(out, d_o, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    return RM_OK;
+}
+
+extern "C" int rm_pca_reduce_windows(rm_ctx *ctx, const float *motion, int n, int first, int window, double *out, void *stream)
+{
+    if (!ctx || !motion || !out || n < 0 || first < 0 || first > n || window < 1) return fail(RM_E_BADARG, "rm_pca_reduce_windows: bad argument");
+    if (first == n) return RM_OK;
+    const int32_t seg[3] = {0, n, first};
+    return pca_windows(ctx, motion, seg, 1, window, n, n - first, out, (hipStream_t)stream);
+}
+
 // seg[k] = {first row of list k inside motion, its number of rows n_k, first_k}: list k's outputs are rm_pca_reduce_windows(its rows,
 // n_k, first_k, window), one list after the other in out.  The lists may leave gaps between them but may not overlap.
 extern "C" int rm_pca_reduce_windows_multi(rm_ctx *ctx, const float *motion, const int32_t *seg, int K, int window, double *out, void *stream)
@@ -669,27 +562,7 @@ extern "C" int rm_pca_reduce_windows_multi(rm_ctx *ctx, const float *motion, con
     }
     if (nout > 0x7fffffffll || (rows > 0 && !motion) || (nout > 0 && !out)) return fail(RM_E_BADARG, "rm_pca_reduce_windows_multi: bad argument");
     if (nout == 0) return RM_OK;
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(ctx->device));
-    // one upload: the rows, behind them the (first row of the list, row inside the list) pair of every output
-    const size_t rows_bytes = (sizeof(float) * 2 * (size_t)rows + 7) / 8 * 8, map_bytes = sizeof(int) * 2 * (size_t)nout;
-    std::vector<uint8_t> up(rows_bytes + map_bytes);
-    std::memcpy(up.data(), motion, sizeof(float) * 2 * (size_t)rows);
-    int *map = (int *)(up.data() + rows_bytes);
-    for (int k = 0; k < K; ++k)
-        for (int j = seg[3 * k + 2]; j < seg[3 * k + 1]; ++j) { *map++ = seg[3 * k]; *map++ = j; }
-    std::string err;
-    uint8_t *d_in = nullptr;
-    double *d_o = nullptr;
-    int rc;
-    if ((rc = ctx->flow.get("pcawm_in", up.size(), (void **)&d_in, err)) < 0) return fail(rc, "%s", err.c_str());
-    if ((rc = ctx->flow.get("pcawm_out", sizeof(double) * (size_t)nout, (void **)&d_o, err)) < 0) return fail(rc, "%s", err.c_str());
-    HIP_TRY(hipMemcpyAsync(d_in, up.data(), up.size(), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_pca_reduce_windows_multi<>, dim3((unsigned)nout), dim3(64), 0, s, (const float *)d_in, (const int *)(d_in + rows_bytes), window, d_o);
-    LAUNCH_CHECK();
-    HIP_TRY(hipMemcpyAsync(out, d_o, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
-    return RM_OK;
+    return pca_windows(ctx, motion, seg, K, window, rows, nout, out, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 """Shared cases of tests/test_emu_flow_multi.py (host-emulated build) and tests/test_gpu_flow_multi.py (the MI355X): builders of
 frames, rectangles and call schedules for rm_flow_multi_clip / rm_pca_reduce_windows_multi / SubjectTracker(motion_extraction_method=
-'flow'), and the comparison of a schedule against the per-subject calls it stands for.  Every comparison is bit for bit.  No test
-functions here.
+'flow'), and the comparison of a schedule against the per-subject calls it stands for.  Every comparison is bit for bit.  The
+reference of a comparison is always the per-frame form ("step": rm_flow_step, kernels and host code of its own): rm_flow_clip is
+the one-subject entry of the code behind rm_flow_multi_clip, so it stands beside "multi" as a subject, never as its reference.
+No test functions here.
 
 An `api` is one of the two adapters below: the same calls on numpy arrays through the emulated C-ABI, or on device tensors through
 respmon_amd.base._Backend."""
@@ -128,6 +130,9 @@ class EmuApi:
     def set_bytes(self, n):
         self.emu.debug_set("flow_clip_bytes", n)
 
+    def pca_one(self, rows):
+        return self.emu.pca_reduce(rows)
+
     def pca(self, rows, first, window):
         from tests.emu_harness import ptr
         m = np.ascontiguousarray(rows, np.float32).reshape(-1, 2)
@@ -185,6 +190,9 @@ class GpuApi:
     def set_bytes(self, n):
         from respmon_amd import device
         device.debug_set("flow_clip_bytes", n)
+
+    def pca_one(self, rows):
+        return self.be.pca_reduce(rows)
 
     def pca(self, rows, first, window):
         return self.be.pca_reduce_windows(rows, first, window)
@@ -246,10 +254,62 @@ def assert_same(got, want, what=""):
 
 
 def assert_same_next_step(api, frame, rois, got, want, what=""):
-    """one further rm_flow_step from every state of both runs: the crops, pyramids and points the calls left agree"""
+    """one further rm_flow_step from every state of both runs: the crops, pyramids and points the calls left agree
+    (got: one run, or a list of runs that are each compared with `want`)"""
     for k, roi in enumerate(rois):
-        a, b = api.step(got["states"][k], frame, roi), api.step(want["states"][k], frame, roi)
-        assert np.array_equal(a[0], b[0]) and a[1] == b[1], ("next step of subject %d" % k, what)
+        b = api.step(want["states"][k], frame, roi)
+        for i, g in enumerate(got if isinstance(got, list) else [got]):
+            a = api.step(g["states"][k], frame, roi)
+            assert np.array_equal(a[0], b[0]) and a[1] == b[1], ("next step of subject %d, run %d" % (k, i), what)
+
+
+def check_alternating_one_subject_clips(api, frames):
+    """One-subject rm_flow_clip calls share the chunk workspace of their context: two states with different pyramid depths (1 and 3
+    LK levels) advance by alternating calls -- A 3 frames, B 3, A 4, B 4 -- unchunked and with 2 frames per chunk, and each must
+    come out as its own 7 rm_flow_step calls: outputs, rm_flow_points and one further step.  frames: 9 of the 80 x 100 frames."""
+    rois = [ROIS_EMU[0], ROIS_EMU[2]]
+    assert [lk_levels(r[3], r[2]) for r in rois] == [1, 3]
+    want = run(api, frames, rois, [("step", 7)])
+    assert all(p is not None and len(p) > 0 for p in want["pts0"]) and (want["n_good"][-1] > 0).all()
+    runs = []
+    for per_chunk in (0, 2):
+        states, pts0 = begin_all(api, frames[0], rois)
+        mean, n_good = np.zeros((7, 2, 2), np.float32), np.zeros((7, 2), np.int32)
+        try:
+            for t, n in ((1, 3), (4, 4)):
+                for k, roi in enumerate(rois):
+                    api.set_bytes(chunk_bytes([roi], per_chunk) if per_chunk else 0)
+                    m, ng = api.clip(states[k], frames[t:t + n], roi)
+                    mean[t - 1:t - 1 + n, k], n_good[t - 1:t - 1 + n, k] = m, ng
+        finally:
+            api.set_bytes(0)
+        got = dict(states=states, pts0=pts0, mean=mean, n_good=n_good, points=[api.points(st, 100) for st in states])
+        assert_same(got, want, ("alternating clips", per_chunk))
+        runs.append(got)
+    assert_same_next_step(api, frames[8], rois, runs, want, "alternating clips")
+
+
+def check_pca_windows_multi(api):
+    """rm_pca_reduce_windows_multi on lists of 0, 1, 2, 5 and 129 rows, each from first = 0, n // 2 and n, at windows of 128 and 5.  The
+    reference is rm_pca_reduce window by window (another kernel); rm_pca_reduce_windows, the K = 1 entry of the same body, beside it.
+    -> the lists {n: rows}"""
+    rng = np.random.default_rng(12)
+    lists = {n: (rng.standard_normal((n, 2)) * rng.uniform(0.01, 2, 2) + rng.uniform(-1, 1, 2)).astype(np.float32) for n in (0, 1, 2, 5, 129)}
+    for window in (128, 5):
+        rows, firsts = [], []
+        for n, md in lists.items():
+            for first in (0, n // 2, n):
+                rows.append(md); firsts.append(first)
+        got = api.pca_multi(rows, firsts, window)
+        assert len(got) == len(rows)
+        for md, first, g in zip(rows, firsts, got):
+            want = np.array([api.pca_one(md[max(0, j + 1 - window):j + 1]) for j in range(first, len(md))])
+            assert np.array_equal(g, want, equal_nan=True), (len(md), first, window)
+            assert np.array_equal(g, api.pca(md, first, window) if len(md) > first else np.empty(0), equal_nan=True), (len(md), first, window)
+        one = api.pca_multi([lists[129]], [3], window)
+        want = np.array([api.pca_one(lists[129][max(0, j + 1 - window):j + 1]) for j in range(3, 129)])
+        assert len(one) == 1 and np.array_equal(one[0], want) and np.array_equal(one[0], api.pca(lists[129], 3, window))
+    return lists
 
 
 # ---- SubjectTracker('flow') against stand-alone monitors ------------------------------------------------------------------------------

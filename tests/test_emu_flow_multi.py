@@ -1,6 +1,7 @@
 """Several subjects by optical flow in one call per clip (rm_flow_multi_clip, rm_pca_reduce_windows_multi,
 SubjectTracker(motion_extraction_method='flow')) on the host-emulated build (tests/emu): each against the per-subject calls it stands
-for, bit for bit (np.array_equal, NaN at the same positions).  The cases are those of tests/flow_multi_cases.py; the GPU twin is
+for, bit for bit (np.array_equal, NaN at the same positions).  The flow reference is the per-frame loop of rm_flow_step; rm_flow_clip,
+the K = 1 entry of the same driver, is compared with it as rm_flow_multi_clip is.  The cases are those of tests/flow_multi_cases.py; the GPU twin is
 tests/test_gpu_flow_multi.py."""
 import numpy as np
 import pytest
@@ -28,20 +29,21 @@ def frames():
 
 @pytest.fixture(scope="module")
 def want(api, frames):
-    """the loop every test compares with: four rm_flow_clip calls of 7 frames (computed once, its states are used for one further step)"""
-    w = fm.run(api, frames, ROIS_EMU, [("clip", 7)])
+    """the loop every test compares with: 7 rm_flow_step calls on each of four states (computed once and left as it is)"""
+    w = fm.run(api, frames, ROIS_EMU, [("step", 7)])
     assert [fm.lk_levels(r[3], r[2]) for r in ROIS_EMU] == [1, 2, 3, 2]
     assert all(p is not None and len(p) > 0 for p in w["pts0"]) and (w["n_good"][-1] > 0).all()     # every subject tracks to the end
     return w
 
 
 def test_emu_flow_multi_equals_the_loop(api, frames, want):
-    got = fm.run(api, frames, ROIS_EMU, [("multi", 7)])
-    fm.assert_same(got, want)
+    got, clips = fm.run(api, frames, ROIS_EMU, [("multi", 7)]), fm.run(api, frames, ROIS_EMU, [("clip", 7)])
+    fm.assert_same(got, want, "multi")
+    fm.assert_same(clips, want, "clip")
     assert np.array_equal(got["mean"][:, 1], got["mean"][:, 3]) and np.array_equal(got["n_good"][:, 1], got["n_good"][:, 3])
     assert np.array_equal(got["points"][1], got["points"][3])
-    fresh = fm.run(api, frames, ROIS_EMU, [("clip", 7)])
-    fm.assert_same_next_step(api, frames[8], ROIS_EMU, got, fresh)
+    fresh = fm.run(api, frames, ROIS_EMU, [("step", 7)])
+    fm.assert_same_next_step(api, frames[8], ROIS_EMU, [got, clips], fresh)
 
 
 @pytest.mark.parametrize("per_chunk", [0, 2, 1])
@@ -53,8 +55,9 @@ def test_emu_flow_multi_any_grouping(api, frames, want, per_chunk):
         for schedule in ([("multi", 3), ("multi", 4)], [("multi", 1), ("multi", 6)], [("step", 1), ("multi", 3), ("clip", 2), ("multi", 1)]):
             got = fm.run(api, frames, rois, schedule)
             fm.assert_same(got, w3, (per_chunk, schedule))
-        loop = fm.run(api, frames, rois, [("clip", 7)])
-        fm.assert_same_next_step(api, frames[8], rois, got, loop, per_chunk)
+        clips = fm.run(api, frames, rois, [("clip", 7)])
+        fm.assert_same(clips, w3, (per_chunk, "clip"))
+        fm.assert_same_next_step(api, frames[8], rois, [got, clips], fm.run(api, frames, rois, [("step", 7)]), per_chunk)
     finally:
         api.set_bytes(0)
 
@@ -78,7 +81,9 @@ def test_emu_flow_multi_unequal_lives(api):
                 assert not got["n_good"][4:, 0].any() and not got["mean"][4:, 0].any() and len(got["points"][0]) == 0
         finally:
             api.set_bytes(0)
-    fm.assert_same_next_step(api, f[8], rois, got, fm.run(api, f, rois, [("clip", 7)], begins))
+    clips = fm.run(api, f, rois, [("clip", 7)], begins)
+    fm.assert_same(clips, loop, "clip")
+    fm.assert_same_next_step(api, f[8], rois, [got, clips], loop)
     again = api.multi(got["states"], f[7:9], rois)            # the dead states go on taking clips
     assert not again[1][:, 0].any() and not again[1][:, 2].any() and again[1][-1, 1] > 0
 
@@ -89,8 +94,9 @@ def test_emu_flow_multi_every_frame_dtype(api, frames, want):
     for f in (f64, f64.astype(np.float32), f64.astype(np.float16)):
         # (a float frame is cropped as float_to_uint8(crop): equal crops for float64; float32 / float16 round k / 255 and may differ)
         got = fm.run(api, f, rois, [("multi", 7)])
-        loop = fm.run(api, f, rois, [("clip", 7)])
-        fm.assert_same(got, loop, f.dtype)
+        loop = fm.run(api, f, rois, [("step", 7)])
+        fm.assert_same(got, loop, (f.dtype, "multi"))
+        fm.assert_same(fm.run(api, f, rois, [("clip", 7)]), loop, (f.dtype, "clip"))
         if f.dtype == np.float64:
             fm.assert_same(got, dict(mean=want["mean"][:, :3], n_good=want["n_good"][:, :3], points=want["points"][:3]), "float64 against uint8")
 
@@ -151,25 +157,18 @@ def test_emu_flow_multi_k_bounds(api, frames, want):
     fm.assert_same(one, dict(mean=want["mean"][:, 1:2], n_good=want["n_good"][:, 1:2], points=want["points"][1:2]))
     rois = [(4 + 9 * (k % 8), 3 + 7 * (k // 8), 24, 20) for k in range(64)]
     got = fm.run(api, frames[:3], rois, [("multi", 2)])
-    loop = fm.run(api, frames[:3], rois, [("clip", 2)])
+    loop = fm.run(api, frames[:3], rois, [("step", 2)])
     assert sum(p is not None for p in loop["pts0"]) >= 32 and (loop["n_good"][-1] > 0).sum() >= 32
-    fm.assert_same(got, loop)
+    fm.assert_same(got, loop, "multi")
+    fm.assert_same(fm.run(api, frames[:3], rois, [("clip", 2)]), loop, "clip")
+
+
+def test_emu_flow_clip_alternating_states_share_the_context(api, frames):
+    fm.check_alternating_one_subject_clips(api, frames)
 
 
 def test_emu_pca_reduce_windows_multi(api):
-    rng = np.random.default_rng(12)
-    lists = {n: (rng.standard_normal((n, 2)) * rng.uniform(0.01, 2, 2) + rng.uniform(-1, 1, 2)).astype(np.float32) for n in (0, 1, 2, 5, 129)}
-    for window in (128, 5):
-        rows, firsts = [], []
-        for n, md in lists.items():
-            for first in (0, n // 2, n):
-                rows.append(md); firsts.append(first)
-        got = api.pca_multi(rows, firsts, window)
-        assert len(got) == len(rows)
-        for md, first, g in zip(rows, firsts, got):
-            assert np.array_equal(g, api.pca(md, first, window) if len(md) > first else np.empty(0), equal_nan=True), (len(md), first, window)
-        one = api.pca_multi([lists[129]], [3], window)
-        assert len(one) == 1 and np.array_equal(one[0], api.pca(lists[129], 3, window))
+    lists = fm.check_pca_windows_multi(api)
     allrows = np.concatenate([lists[5], lists[129]])
     B = _capi.RM_E_BADARG
     ok = [(0, 5, 0), (5, 129, 2)]

@@ -1,6 +1,8 @@
 """Several subjects by optical flow in one call per clip on the GPU (rm_flow_multi_clip, rm_pca_reduce_windows_multi,
-SubjectTracker(motion_extraction_method='flow')) at real sizes, against the per-subject calls bit for bit.  The cases and the
-comparison are those of tests/flow_multi_cases.py; the host-emulated twin with the refusals is tests/test_emu_flow_multi.py."""
+SubjectTracker(motion_extraction_method='flow')) at real sizes, against the per-subject calls bit for bit: the per-frame
+rm_flow_step loop is the reference, rm_flow_clip (the K = 1 entry of the same driver) is compared with it as the multi call is;
+the windowed PCA of several lists against rm_pca_reduce window by window.  The cases and the comparison are those of
+tests/flow_multi_cases.py; the host-emulated twin with the refusals is tests/test_emu_flow_multi.py."""
 import numpy as np
 import pytest
 
@@ -47,16 +49,17 @@ def test_flow_multi_real_sizes(api, dtype):
         finally:
             api.set_bytes(0)
         fm.assert_same(got, steps, (per_chunk, schedule))
-    fm.assert_same_next_step(api, frames[25], rois, got, clips)
+    fm.assert_same_next_step(api, frames[25], rois, [got, clips], steps)
 
 
 def test_flow_multi_1080p_16_subjects(api):
     """the stride arithmetic at frame scale: 1080p uint8, 12 frames, 16 overlapping rectangles of 351 x 235"""
     frames = api.dev(_texture_clip(1080, 1920, 13, seed=7))
     rois = fm.grid_rois(16, 1080, 1920)
-    loop = fm.run(api, frames, rois, [("clip", 12)])
+    loop = fm.run(api, frames, rois, [("step", 12)])
     assert all(p is not None and len(p) >= 20 for p in loop["pts0"]) and (loop["n_good"][-1] > 0).all()
-    fm.assert_same(fm.run(api, frames, rois, [("multi", 12)]), loop)
+    fm.assert_same(fm.run(api, frames, rois, [("multi", 12)]), loop, "multi")
+    fm.assert_same(fm.run(api, frames, rois, [("clip", 12)]), loop, "clip")
 
 
 def test_flow_multi_both_finish_paths(api):
@@ -67,10 +70,11 @@ def test_flow_multi_both_finish_paths(api):
     frames = api.dev(np.stack([render(0.3 * t, -0.2 * t) for t in range(4)]))
     rois = [(0, 0, W, H), (100, 200, 351, 235)]
     begins, caps = [(6100, 0.001, 1, 7), BEGIN], [6100, 100]
-    loop = fm.run(api, frames, rois, [("clip", 3)], begins, caps)
+    loop = fm.run(api, frames, rois, [("step", 3)], begins, caps)
     assert len(loop["pts0"][0]) == 6100 and len(loop["pts0"][1]) == 100 and (loop["n_good"][-1] > [3000, 50]).all()
-    fm.assert_same(fm.run(api, frames, rois, [("multi", 3)], begins, caps), loop)
-    fm.assert_same(fm.run(api, frames, rois, [("multi", 1), ("multi", 2)], begins, caps), loop)
+    fm.assert_same(fm.run(api, frames, rois, [("multi", 3)], begins, caps), loop, "multi")
+    fm.assert_same(fm.run(api, frames, rois, [("multi", 1), ("multi", 2)], begins, caps), loop, "multi 1 + 2")
+    fm.assert_same(fm.run(api, frames, rois, [("clip", 3)], begins, caps), loop, "clip")
 
 
 def test_flow_multi_unequal_lives(api):
@@ -89,7 +93,17 @@ def test_flow_multi_unequal_lives(api):
                 fm.assert_same(got, loop, (per_chunk, schedule))
         finally:
             api.set_bytes(0)
-    fm.assert_same_next_step(api, frames[8], rois, got, fm.run(api, frames, rois, [("clip", 7)], begins))
+    clips = fm.run(api, frames, rois, [("clip", 7)], begins)
+    fm.assert_same(clips, loop, "clip")
+    fm.assert_same_next_step(api, frames[8], rois, [got, clips], loop)
+
+
+def test_flow_clip_alternating_states_share_the_context(api):
+    fm.check_alternating_one_subject_clips(api, api.dev(fm.frames_emu(1.0)))
+
+
+def test_pca_reduce_windows_multi(api):
+    fm.check_pca_windows_multi(api)
 
 
 def _monitor(frames, roi):

@@ -7,7 +7,9 @@ alternating.
   roi_mean  one rm_roi_mean_multi_clip call against K rm_roi_mean_clip calls (outputs asserted equal before anything is timed)
   locate    rm_locate_multi(max_rois = K) against rm_locate on a buffer with sixteen breathing blobs (entry 0 asserted equal)
   flow      one rm_flow_multi_clip + one rm_pca_reduce_windows_multi against K rm_flow_clip + K rm_pca_reduce_windows, 100 corners per
-            subject on textured frames, K fresh states per repetition (begun outside the timed part; outputs asserted equal first)
+            subject on textured frames, K fresh states per repetition (begun outside the timed part; outputs asserted equal first).
+            rm_flow_clip and rm_pca_reduce_windows are the K = 1 entries of the code behind the multi calls, so at K = 1 both forms
+            time one code path against itself (a check of the noise, not a comparison); K = 4 and K = 16 compare one call with K.
 Prints one JSON line: milliseconds per call of both forms (the median of the alternating repetitions).  No threshold is set on
 these figures: they are recorded."""
 import argparse
