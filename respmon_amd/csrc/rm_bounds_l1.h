@@ -527,7 +527,7 @@ template <int S>
 __global__ __launch_bounds__(256) void k_bounds_up1(const double *cS, ChainGeom g, int ntiles, double *lo, double *hi)
 {
     static_assert(S == 3 || S == 4, "skip 3 / 4 (skip 2 has the streaming kernels above)");
-    using F = TileFoot<S, false>;
+    using F = TileFoot<S>;
     constexpr int K = S - 1;
     constexpr int NRD = F::nr(K), NCD = F::nc(K);   // the footprint at level S - 1: 5 x 11 (skip 4), 7 x 19 (skip 3)
     constexpr int NRS = F::nr(S), NCS = F::nc(S);   // the level-S block it is formed from: 4 x 7, 5 x 11

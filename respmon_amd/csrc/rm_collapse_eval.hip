@@ -47,7 +47,7 @@ int launch_eval_pairs(rm_ctx *ctx, const CollapsePlan &cp, hipStream_t s)
 #endif
 #define RM_EVAL_FAST(SS)                                                                                                              \
         do {                                                                                                                          \
-            using FootE = TileFoot<SS, false>;                                                                                        \
+            using FootE = TileFoot<SS>;                                                                                               \
             hipLaunchKernelGGL((k_eval_pairs_fast<SS>), dim3(fgrid), dim3(64), sizeof(double) * FootE::TOTAL, s, sl.cS, g, ntiles, cp.list_a, cp.list_b, \
                                cp.slot_of, st, cp.store, sp, Th);                                                                     \
         } while (0)
@@ -132,8 +132,6 @@ int collapse_eval(rm_ctx *ctx, const SmallLevels &sl, int T, int t0, int t1, dou
     ctx->dbg_pairs = npairs; ctx->dbg_cap = cap; ctx->dbg_mine = npairs_mine; ctx->dbg_mode = sp.mode; ctx->dbg_auto_dense = sp.auto_dense_ok;
     RM_TRY(ws(ctx, "sel_cnt", (size_t)ntiles, &cp.sel_cnt));
     RM_TRY(ws(ctx, "heavy_tiles", (size_t)ntiles, &cp.heavy));
-    cp.xs_tab = nullptr;
-    if (ctx->dbg.xs && tile_eval_ok(g) && !cp.fused) RM_TRY(ws(ctx, "xs_tab", (size_t)npairs, &cp.xs_tab));   // exception store (rm_xstore.h): one entry per pair
     ctx->dbg_cS = sl.cS; ctx->dbg_cS_bytes = sizeof(double) * (size_t)Th * g.h[g.S] * g.w[g.S];   // (after this call's last ws(): rm_debug_workspace "cS")
     if (!sl.bounds_ready) {
         // per-frame separable form, in bands of tile rows whose row-extrema table fits 64 KB of LDS; the per-pair kernel
@@ -197,7 +195,7 @@ int collapse_eval(rm_ctx *ctx, const SmallLevels &sl, int T, int t0, int t1, dou
     }
     const int prune_ok = (!no_prune && thr >= 0.0 && thr <= 1.0) ? 1 : 0;
     hipLaunchKernelGGL(k_select_pairs<>, dim3((ntiles + SEL_TILES - 1) / SEL_TILES, (Th + SEL_PH * SEL_U - 1) / (SEL_PH * SEL_U)), dim3(256), 0, s,
-                       cp.lo, cp.hi, ntiles, Th, T, t0, t1, st, cp.list_a, cp.list_b, cp.slot_of, prune_ok ? 0 : 1, thr, cp.sel_cnt, cp.heavy, cp.xs_tab);
+                       cp.lo, cp.hi, ntiles, Th, T, t0, t1, st, cp.list_a, cp.list_b, cp.slot_of, prune_ok ? 0 : 1, thr, cp.sel_cnt, cp.heavy);
     LAUNCH_CHECK();
     if (cp.fused) {
         // exact extrema from the C pairs: one wave per pair, a grid that covers the few pairs of a pruned selection at once and loops
@@ -206,7 +204,7 @@ int collapse_eval(rm_ctx *ctx, const SmallLevels &sl, int T, int t0, int t1, dou
         ctx->dbg_fused = 1;
 #define RM_EVAL_C(SS)                                                                                            \
         do {                                                                                                     \
-            using FootC = TileFoot<SS, false>;                                                                   \
+            using FootC = TileFoot<SS>;                                                                          \
             hipLaunchKernelGGL((k_eval_c<SS>), dim3(cgrid), dim3(64), sizeof(double) * FootC::TOTAL, s, sl.cS, g, ntiles, cp.list_a, st); \
         } while (0)
         switch (sl.S) { case 1: RM_EVAL_C(1); break; case 2: RM_EVAL_C(2); break; case 3: RM_EVAL_C(3); break; default: RM_EVAL_C(4); break; }

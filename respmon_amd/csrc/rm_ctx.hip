@@ -117,9 +117,6 @@ extern "C" int rm_debug_set(rm_ctx *ctx, const char *key, long long value)
     else if (k == "bounds_l1") d.bounds_l1 = (int)value;
     else if (k == "bounds_up1") d.bounds_up1 = (int)value;
     else if (k == "dense_wf_list") d.dense_wf_list = (int)value;
-    else if (k == "xs") d.xs = (int)value;
-    else if (k == "xs_waves") d.xs_waves = (int)value;
-    else if (k == "xs_budget_words") d.xs_budget_words = value;
     else if (k == "bounds_l1_rows") d.bounds_l1_rows = (int)value;
     else if (k == "dense_rows") d.dense_rows = (int)value;
     else if (k == "dense_general") d.dense_general = (int)value;
@@ -134,8 +131,6 @@ extern "C" int rm_debug_set(rm_ctx *ctx, const char *key, long long value)
     else if (k == "store_slots") d.store_slots = value;
     else if (k == "store_default_slots") d.store_default_slots = value;
     else if (k == "collapse_fused") d.collapse_fused = (int)value;
-    else if (k == "tile_sum_half") d.tile_sum_half = (int)value;
-    else if (k == "dense_tiles") d.dense_tiles = (int)value;
     else if (k == "eval_fast") d.eval_fast = (int)value;
     else if (k == "exchange_dense") d.exchange_dense = (int)value;
     else if (k == "host_simple_shape") d.host_simple_shape = (int)value;
@@ -150,8 +145,6 @@ extern "C" int rm_debug_set(rm_ctx *ctx, const char *key, long long value)
     else if (k == "ccl_tiles") d.ccl_tiles = (int)value;
     else if (k == "ccl_tile_waves") d.ccl_tile_waves = (int)value;
     else if (k == "label_host_steps") d.label_host_steps = value;
-    else if (k == "sum_sym") d.sum_sym = (int)value;
-    else if (k == "sum_rows") d.sum_rows = (int)value;
     else if (k == "flow_clip_bytes") d.flow_clip_bytes = value;
     else return fail(RM_E_BADARG, "rm_debug_set: unknown key '%s'", key);
     return RM_OK;

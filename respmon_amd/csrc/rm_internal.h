@@ -43,7 +43,6 @@
 #include "rm_dense_sum.h"
 #include "rm_tile_eval.h"
 #include "rm_bounds_l1.h"
-#include "rm_xstore.h"
 #include "rm_ccl.h"
 #include "rm_flow.h"
 #include "rm_subjects.h"
@@ -81,10 +80,9 @@ struct CollapsePlan {
     int T = 0, t0 = 0, t1 = 0, H = 0, W = 0, S = 0;
     bool valid = false;
     bool no_prune = false;
-    bool fused = false;                    // k_eval_c + k_tile_sum (rm_tile_eval.h): no value store, no separate evaluation of the kept pairs
+    bool fused = false;                    // k_eval_c + k_dense_sum_t (rm_tile_eval.h): no value store, no separate evaluation of the kept pairs
     SumPlan sp{0, 0, 0, 0};                // sparse or dense sum: decided on the device (rm_kernels.h sum_is_dense)
     bool l1_bounds = false;                // lo / hi are the extrema of the LEVEL-1 footprints (rm_bounds_l1.h): a pair they keep cannot stop at level 1
-    unsigned long long *xs_tab = nullptr;  // exception store table [tile][unique frame] (rm_xstore.h XsEntry), written XS_NONE by k_select_pairs
 };
 
 
@@ -99,9 +97,6 @@ struct DebugKnobs {
     long long bounds_table_bytes = 0;   // > 0: LDS budget of k_frame_bounds' row-extrema table (forces small bands)
     int bounds_l1 = 2;            // skip 2: tile bounds from the level-1 footprint (rm_bounds_l1.h) -- 2: formed in packed float32 and widened (default), 1: in float64 (the exact extrema); 0: from the level-2 footprint (k_frame_bounds / k_frame_bounds_rows)
     int bounds_l1_rows = 0;       // > 0: tile rows per wave of k_frame_bounds_l1 (default: 16, fewer on small frames)
-    int xs = 0;                   // 1: dense selections go through the exception store (rm_xstore.h) instead of the store-less sum kernels (measured slower: DESIGN 7)
-    int xs_waves = 0;             // 1 / 2 / 4: waves per tile of k_xs_sum (0: by the number of tiles)
-    long long xs_budget_words = 0;   // > 0: capacity of the exception store in 8-byte words (default: the worst case of the geometry, at most 1 GiB)
     int dense_wf_list = 1;        // 0: k_dense_sum_wf evaluates every frame of a tile (no kept list from slot_of / lo)
     int bounds_up1 = -1;          // skip 3 / 4: bounds refined from the level-(S - 1) footprint (k_bounds_up1): 1 always, 0 never, -1 behind a call that kept many pairs (ctx->refine_hint)
     int bounds_scalar = 0;        // 1: k_frame_bounds (a thread per row and tile column) also for wide levels instead of k_frame_bounds_rows
@@ -114,9 +109,7 @@ struct DebugKnobs {
     int dc_prio_shift = 0;        // 1 .. 12: log2 of the rotation period of dc_prio 2 in input rows (default 4)
     int dc_prio = 2;              // k_down_chain: issue priority of its waves (2 rotating -- the default --, 0 none, 1 younger workgroups higher, 3 older higher)
     int dc_split = 0;             // > 0: share (per mille) of the level-S rows the upper of exactly two segments takes (default 513)
-    int collapse_fused = 0;       // 1: collapse passes without a value store wherever TileEval applies (rm_tile_eval.h k_eval_c + k_tile_sum); 0: only as the stand-in for an overflowing store at skip >= 3
-    int sum_rows = 0;             // 1: k_masked_sum_rows (one wave per tile row, LDS-DMA staging) instead of k_masked_sum_tiles for whole-buffer sums (measured slower: 35 us against 21)
-    int sum_sym = 0;              // 1: k_masked_sum_sym instead of k_masked_sum_tiles for whole-buffer sums (measured slower: 31 us against 21 at 1080p x 256)
+    int collapse_fused = 0;       // 1: collapse passes without a value store wherever TileEval applies (rm_tile_eval.h k_eval_c + k_dense_sum_t); 0: only as the stand-in for an overflowing store at skip >= 3
     long long label_host_steps = 0;   // > 0: border steps of an unlabelled host stage beyond which the next extraction is labelled on the device (default LABEL_MIN_STEPS)
     int ccl_tiles = 1;            // 0: rows of whole words labelled through global memory as the others are (k_ccl_union / k_ccl_bbox), not tile by tile in LDS
     int ccl_tile_waves = 0;       // waves of a k_ccl_tile workgroup (4 / 8 / 16: eight / four / two rows of the tile per wave; 0: by the number of tiles)
@@ -131,8 +124,6 @@ struct DebugKnobs {
     int eval_fast = 1;            // 0: the generic k_eval_pairs instead of k_eval_pairs_fast (rm_tile_eval.h) where the latter applies
     int dense_exact_top = 1;      // 0: the store-less sum kernels evaluate every pair the selection kept (no second look with the exact `top`)
     int dense_t_low = -1;         // k_dense_sum_t (TileEval) at skip <= 2 instead of k_dense_sum_w / wf: 1 always, 0 never, -1 on large frames
-    int dense_tiles = 1;          // 0: k_tile_sum (rounds of sixteen waves per tile) instead of k_dense_sum_t (one wave per tile) where a store-less sum at skip >= 3 is due
-    int tile_sum_half = -1;       // 0 / 1: k_tile_sum works on whole tiles / half tiles whatever the number of heavy tiles (-1: by that number)
     long long store_default_slots = 0;   // > 0: slots the value store starts with before any selection has made it grow (default 16 384)
     long long store_slots = 0;    // > 0: capacity of the value store in (tile, frame) slots (forces the overflow path)
     long long flow_clip_bytes = 0;   // > 0: workspace cap of one chunk of rm_flow_clip / rm_flow_multi_clip (default 256 MiB): a chunk holds max(1, cap / slot - 1) frames, slot = 5 bytes per pixel of every LK pyramid level of the ROI (summed over the subjects that still have points)

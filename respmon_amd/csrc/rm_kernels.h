@@ -1064,8 +1064,6 @@ struct CollapseState {
     double min_val, max_val, top;   // transforms.py:185-189, decoded by k_finish_minmax
     unsigned long long heat_min_key, heat_max_key;
     double sp_bg;                   // sparse merge: rank-ordered sum of the packets' backgrounds (k_sparse_index)
-    unsigned long long xs_next;     // exception store (rm_xstore.h): words handed out so far
-    unsigned int xs_overflow;       // ... a record did not fit: the store-less kernel behind k_xs_sum takes the sum
 };
 
 __device__ void state_init_lane(CollapseState *st, int i)   // lanes 0 .. NSTRIPE-1 of one wavefront
@@ -1080,7 +1078,6 @@ __device__ void state_init_lane(CollapseState *st, int i)   // lanes 0 .. NSTRIP
     st->min_key = ~0ull; st->max_key = 0ull; st->n_list_a = 0; st->n_list_b = 0; st->n_slots = 0; st->n_heavy = 0;
     st->margin = 0; st->top_ub = 0; st->min_val = 0; st->max_val = 0; st->top = 0;
     st->heat_min_key = ~0ull; st->heat_max_key = 0ull;
-    st->xs_next = 0ull; st->xs_overflow = 0u;
 }
 
 RM_KERNEL __launch_bounds__(NSTRIPE) void k_state_init(CollapseState *st) { state_init_lane(st, (int)threadIdx.x); }
@@ -1660,7 +1657,7 @@ __device__ __forceinline__ unsigned long long block_excl_scan_256(unsigned long 
 constexpr int SEL_TILES = 16, SEL_PH = 16, SEL_U = 9;   // 16 x 9 = 144 unique frames per chunk: one chunk at T = 256
 RM_KERNEL __launch_bounds__(256) void k_select_pairs(const double *lo, const double *hi, int ntiles, int Th, int T, int t0, int t1,
                                                       CollapseState *st, unsigned int *list_a, unsigned int *list_b, int *slot_of,
-                                                      int no_prune, double thr, int *sel_cnt, unsigned int *heavy, unsigned long long *xs_tab)
+                                                      int no_prune, double thr, int *sel_cnt, unsigned int *heavy)
 {
     RM_TRACE_SCOPE(4);
     __shared__ unsigned long long s_cnt[256], s_off[257], s_wave[4];
@@ -1754,7 +1751,6 @@ RM_KERNEL __launch_bounds__(256) void k_select_pairs(const double *lo, const dou
         const unsigned int i = (unsigned)u * (unsigned)ntiles + (unsigned)tile;
         const bool isC = (fC >> k) & 1u, isD = (fD >> k) & 1u;
         slot_of[slot_index(u, tile, Th)] = isD ? (int)oD : SLOT_PRUNED;
-        if (xs_tab) xs_tab[slot_index(u, tile, Th)] = 0x00000000ffffffffull;   // XsEntry{XS_NONE, 0}: no exception record yet (rm_xstore.h)
         if (isD) ++oD;
         if (isC) list_a[oA++] = i;
         else if (isD) list_b[oB++] = i;

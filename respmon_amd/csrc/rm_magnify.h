@@ -209,7 +209,7 @@ __device__ __forceinline__ void mag_store(Tout *p, int nvalid, const MagIn<Tin, 
 template <int S, typename Tin, typename Tout>
 __global__ __launch_bounds__(64) void k_magnify(const double *cS, ChainGeom g, int T, int ntiles, const Tin *frames, Tout *out, int vec)
 {
-    using F = TileFoot<S, false>;
+    using F = TileFoot<S>;
     using G = MagGeom<Tin, Tout>;
     static_assert(F::TOTAL <= MAG_LDS_DOUBLES, "the footprint slice must fit under the tile's values");
     HIP_DYNAMIC_SHARED(double, lds)
@@ -220,8 +220,8 @@ __global__ __launch_bounds__(64) void k_magnify(const double *cS, ChainGeom g, i
     const int u0 = chunk * MAG_FC, u1 = min(Th, u0 + MAG_FC);
     const int H0 = g.h[0], W0 = g.w[0];
     const size_t fs = (size_t)g.h[S] * g.w[S], npix = (size_t)H0 * W0;
-    TileSetup<S, false> ts;
-    tile_setup<S, false>(g, tx, ty, 0, lane, ts);
+    TileSetup<S> ts;
+    tile_setup<S>(g, tx, ty, lane, ts);
     // where this lane's pixels of pass p lie: element e = (64 p + lane) V of the tile's 64 x 16 values, row e / 64, column e % 64
     size_t px_off[G::NP];
     int nvalid[G::NP];
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(64) void k_magnify(const double *cS, ChainGeom g, i
         for (int p = 0; p < F::PF; ++p) if (lane + 64 * p < F::NST) lds[F::off(S) + lane + 64 * p] = stg[p];
         wave_sync();
         double v[16];
-        tile_eval<S, false>(ts, lds, lane, v);
+        tile_eval<S>(ts, lds, lane, v);
         wave_sync();   // every lane has its values: the slice may be overwritten
         {   // lane (column pair cp, row half rg) holds rows 8 rg .. 8 rg + 7 of columns 2 cp, 2 cp + 1 (tile_setup)
             double *d = lds + (size_t)(8 * (lane >> 5)) * CT_W + 2 * (lane & 31);

@@ -553,7 +553,6 @@ def test_emu_dense_sum_equals_sparse_path(emu):
     selection / value-store path (flags=256), bit for bit -- every super-tile shape (RM_DENSE_ROWS), skip 1..5, shards of the
     frame range, exhaustive evaluation (flags | 1), and the automatic choice (second call of a geometry that kept every pair)."""
     rng = np.random.default_rng(5)
-    emu.debug_set("xs", 0)            # (the store-less kernels themselves: the exception store that stands in front of them has its own test below)
     for n, (T, H, W, L, S) in enumerate([(4, 64, 96, 4, 2), (3, 67, 131, 5, 3), (3, 48, 64, 3, 1), (2, 100, 160, 7, 5),
                                          (3, 70, 300, 4, 2)]):     # (the GPU twin in tests/test_gpu_calibration.py runs more and larger ones)
         v = rng.random((T, H, W))
@@ -618,7 +617,6 @@ def test_emu_dense_sum_equals_sparse_path(emu):
         a = emu.locate_sharded(v, world, levels=4, skip=2, flags=256)
         b = emu.locate_sharded(v, world, levels=4, skip=2, flags=128)
         assert a[0] == b[0] and np.array_equal(a[1], b[1]), world
-    emu.debug_set("xs", 1)
 
 
 def test_emu_filter_first_per_level_equals_fused(emu):
@@ -787,9 +785,10 @@ def test_emu_contour_stage_device_labelling(emu, oracle):
 
 
 def test_emu_fused_collapse_equals_store_path(emu, oracle):
-    """rm_tile_eval.h (round 4): the store-less collapse passes -- k_eval_c (exact extrema from the C pairs) + k_tile_sum (every kept
-    pair evaluated where it is summed, tile by tile, whole tiles or half tiles) -- against the selection / value-store path
-    (flags=256), bit for bit: skip 1..4, ragged geometries whose virtual footprints meet every border rule (top row, rows past the
+    """rm_tile_eval.h: the flat evaluation with the wave-private evaluator (k_eval_pairs_fast + k_masked_sum_tiles) and the store-less
+    collapse passes -- k_eval_c (exact extrema from the C pairs) + k_dense_sum_t (every kept pair evaluated where it is summed, one
+    wave per tile, frame after frame) -- against the generic selection / value-store path (k_eval_pairs + k_masked_sum_tiles,
+    flags=256), bit for bit: skip 1..4, ragged geometries whose virtual footprints meet every border rule (top row, rows past the
     bottom, left / right columns, 2-row / 2-column levels), exhaustive evaluation, frame shards, and the oracle's ROI."""
     rng = np.random.default_rng(11)
     cases = [(3, 64, 96, 6, 4), (3, 67, 131, 5, 3), (3, 48, 64, 3, 1), (3, 70, 130, 4, 2), (2, 31, 193, 7, 4)]   # (the GPU twin of this test, tests/test_gpu_calibration.py, runs more and larger geometries)
@@ -797,56 +796,24 @@ def test_emu_fused_collapse_equals_store_path(emu, oracle):
         for (T, H, W, L, S) in cases:
             v = rng.random((T, H, W))
             emu.debug_set("collapse_fused", 0)
-            emu.debug_set("eval_fast", 0)            # the generic chain in LDS (k_eval_pairs): the reference of both newer forms
-            emu.debug_set("sum_sym", 0)              # ... and the sum that fetches every visit of a frame (k_masked_sum_tiles)
-            emu.debug_set("sum_rows", 0)
+            emu.debug_set("eval_fast", 0)            # the generic chain in LDS (k_eval_pairs) + k_masked_sum_tiles: the reference of the newer forms
             store, mm = emu.calibrate(v, 10.0, levels=L, skip=S, flags=256)
-            emu.debug_set("sum_rows", 1)             # one wave per (tile, row), unique frames staged through LDS (k_masked_sum_rows)
-            rows, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, flags=256)
-            assert np.array_equal(rows, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "k_masked_sum_rows")
-            emu.debug_set("sum_rows", 0)
-            emu.debug_set("sum_sym", 1)              # unique frames loaded once, added on the way up and down (k_masked_sum_sym)
-            sym, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, flags=256)
-            assert np.array_equal(sym, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "k_masked_sum_sym")
-            emu.debug_set("sum_sym", 0)
-            tiny, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, flags=4)   # an 8-slot store overflows: k_tile_sum stands in at skip >= 3
+            tiny, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, flags=4)   # an 8-slot store overflows: k_dense_sum_t stands in at skip >= 3
             assert np.array_equal(tiny, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "store overflow")
             emu.debug_set("eval_fast", 1)            # the same flat pass with the wave-private evaluator (k_eval_pairs_fast)
             fast, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, flags=256)
             assert np.array_equal(fast, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "k_eval_pairs_fast")
             fast, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, flags=256 | 1)
             assert np.array_equal(fast, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "k_eval_pairs_fast, no_prune")
-            emu.debug_set("collapse_fused", 1)
-            emu.debug_set("dense_tiles", 1)          # one wave per tile, frame after frame (k_dense_sum_t)
+            emu.debug_set("collapse_fused", 1)       # one wave per tile, frame after frame (k_eval_c + k_dense_sum_t)
             dense_t, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S)
             assert np.array_equal(dense_t, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "k_dense_sum_t")
-            emu.debug_set("dense_tiles", 0)          # rounds of sixteen waves per tile (k_tile_sum)
-            for half in (0, 1):     # whole-tile / half-tile work items (chosen by the number of heavy tiles otherwise)
-                emu.debug_set("tile_sum_half", half)
-                fused, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S)
-                assert np.array_equal(fused, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "fused", half)
-            emu.debug_set("tile_sum_half", -1)
             fused, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, flags=1)
-            assert np.array_equal(fused, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "fused, no_prune")
+            assert np.array_equal(fused, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "k_dense_sum_t, no_prune")
             emu.debug_set("collapse_fused", 0)
             auto, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S)
             assert np.array_equal(auto, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "default")
-        # more kept unique frames than one batch of k_masked_sum_sym holds (48): several batches up, the same ones down again
-        for (T, H, W, L, S) in [(101, 20, 70, 5, 3)]:
-            v = rng.random((T, H, W))
-            emu.debug_set("collapse_fused", 0)
-            emu.debug_set("sum_sym", 0)
-            emu.debug_set("sum_rows", 0)
-            store, mm = emu.calibrate(v, 10.0, levels=L, skip=S, flags=256)
-            emu.debug_set("sum_sym", 1)
-            sym, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, flags=256)
-            emu.debug_set("sum_sym", 0)
-            assert np.array_equal(sym, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "k_masked_sum_sym, batches")
-            emu.debug_set("sum_rows", 1)
-            rows, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, flags=256)
-            assert np.array_equal(rows, store) and tuple(mm) == tuple(mm2), (T, H, W, L, S, "k_masked_sum_rows, chunks")
-        emu.debug_set("sum_rows", 0)
-        # a breathing video: few heavy tiles (half-tile work items), pruned pairs in between, and the oracle's ROI
+        # a breathing video: few heavy tiles, pruned pairs in between, and the oracle's ROI
         from respmon_amd import synth
         v8 = synth.synth_breathing(16, 80, 128, seed=3)
         fr = oracle.uint8_to_float(v8)
@@ -854,15 +821,8 @@ def test_emu_fused_collapse_equals_store_path(emu, oracle):
             emu.debug_set("collapse_fused", 0)
             store, mm = emu.calibrate(fr, 10.0, levels=L, skip=S, flags=256)
             emu.debug_set("collapse_fused", 1)
-            emu.debug_set("dense_tiles", 1)
             dense_t, mm2 = emu.calibrate(fr, 10.0, levels=L, skip=S)
             assert np.array_equal(dense_t, store) and tuple(mm) == tuple(mm2), (L, S, "breathing video, k_dense_sum_t")
-            emu.debug_set("dense_tiles", 0)
-            for half in (0, 1):
-                emu.debug_set("tile_sum_half", half)
-                fused, mm2 = emu.calibrate(fr, 10.0, levels=L, skip=S)
-                assert np.array_equal(fused, store) and tuple(mm) == tuple(mm2), (L, S, "breathing video", half)
-            emu.debug_set("tile_sum_half", -1)
             assert emu.locate(fr, 10.0, levels=L, skip=S) == oracle.locate(fr, 10, pyramid_levels=L, skip_levels_at_top=S)
             # frame shards: partial time sums of the store-less path equal the store path's
             for world in (3,):
@@ -873,11 +833,7 @@ def test_emu_fused_collapse_equals_store_path(emu, oracle):
                 assert r0 == r1 and np.array_equal(h0, h1) and tuple(m0) == tuple(m1), (L, S, world, "sharded")
     finally:
         emu.debug_set("collapse_fused", 0)
-        emu.debug_set("tile_sum_half", -1)
         emu.debug_set("eval_fast", 1)
-        emu.debug_set("sum_sym", 0)
-        emu.debug_set("sum_rows", 0)
-        emu.debug_set("dense_tiles", 1)
 
 
 def _roi_shapes(rng):
@@ -1056,42 +1012,28 @@ def test_emu_labelling_rule_counts_not_clocks(emu, oracle):
     assert lab == [(1000, 0), (1000, 1), (1000, 1), (1000, 1), (0, 0), (0, 0), (0, 0), (0, 0)], lab
 
 
-def test_emu_exception_store(emu, oracle):
-    """rm_xstore.h (round 6): a dense selection's masked time sum through the exception store -- every kept pair evaluated once by a
-    flat pass (k_xs_eval), its values below `top` parked in a compact record, the time-ordered additions by k_xs_sum with 1 / 2 / 4
-    waves per tile -- against the value-store path (flags=256), bit for bit: few exceptions per pair (they travel with the record's
-    header) and many (fetched from the record), ragged tiles, skip 1 .. 4, exhaustive evaluation, frame shards, a store that
-    overflows (the store-less kernel behind k_xs_sum takes over), and the oracle's heatmap."""
+def test_emu_dense_selection_few_and_many_values_below_top(emu, oracle):
+    """A dense selection's masked time sum by the store-less kernels (k_dense_sum_w / wf at skip <= 2, k_dense_sum_t above) -- forced
+    (flags=128), exhaustive (flags=128 | 1) and as the stand-in for an overflowing value store (flags=4) -- against the value-store
+    path (flags=256), bit for bit, extrema included: few values below `top` per pair and many, a half-quiet video, ragged tiles,
+    skip 1 .. 4, and the oracle's heatmap."""
     rng = np.random.default_rng(97)
     cases = [(6, 64, 96, 4, 2, 0.7), (5, 67, 131, 5, 3, 0.7), (4, 48, 64, 3, 1, 0.7), (5, 100, 160, 6, 4, 0.7), (7, 70, 300, 4, 2, 0.05),
              (4, 33, 70, 4, 2, 0.3), (9, 40, 200, 5, 2, 0.02), (3, 5, 7, 4, 2, 0.7)]
     for n, (T, H, W, L, S, thr) in enumerate(cases):
         v = rng.random((T, H, W))
-        v[:, H // 3:, W // 4:] *= 0.2                       # a quieter part: fewer exceptions there
-        emu.debug_set("xs", 1)
+        v[:, H // 3:, W // 4:] *= 0.2                       # a quieter part: fewer values below top there
         want, mm = emu.calibrate(v, 10.0, levels=L, skip=S, thr=thr, flags=256)
-        for nw in (1, 2, 4):
-            emu.debug_set("xs_waves", nw)
-            got, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, thr=thr, flags=128)
-            assert np.array_equal(got, want) and tuple(mm) == tuple(mm2), (T, H, W, L, S, thr, nw)
-        emu.debug_set("xs_waves", 0)
+        dense, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, thr=thr, flags=128)
+        assert np.array_equal(dense, want) and tuple(mm) == tuple(mm2), (T, H, W, L, S, thr, "dense")
         got, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, thr=thr, flags=128 | 1)
         assert np.array_equal(got, want) and tuple(mm) == tuple(mm2), (T, H, W, L, S, thr, "no prune")
         got, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, thr=thr, flags=4)      # (an 8-slot value store overflows: the dense route, decided on the device)
         assert np.array_equal(got, want) and tuple(mm) == tuple(mm2), (T, H, W, L, S, thr, "value store overflow")
-        emu.debug_set("xs_budget_words", 3000)             # the exception store itself overflows: the store-less kernel takes the sum
-        got, mm2 = emu.calibrate(v, 10.0, levels=L, skip=S, thr=thr, flags=128)
-        emu.debug_set("xs_budget_words", 0)
-        assert np.array_equal(got, want) and tuple(mm) == tuple(mm2), (T, H, W, L, S, thr, "exception store overflow")
         if n in (0, 4):
             raw = oracle.eulerian_magnification_bandpass(v.copy(), 10.0, 0.1, 1.0, 500.0, pyramid_levels=L, skip_levels_at_top=S, threshold=thr)[0]
             ref = np.average(raw, axis=0)
-            assert np.abs(got - ref).max() <= 1e-9 * max(np.abs(ref).max(), 1e-300), (T, H, W, "oracle")
-    v = rng.random((11, 70, 150))
-    for world in (2, 3):                      # frame shards: partial sums over [t0, t1) with the global extrema
-        a = emu.locate_sharded(v, world, levels=4, skip=2, flags=256)
-        b = emu.locate_sharded(v, world, levels=4, skip=2, flags=128)
-        assert a[0] == b[0] and np.array_equal(a[1], b[1]), world
+            assert np.abs(dense - ref).max() <= 1e-9 * max(np.abs(ref).max(), 1e-300), (T, H, W, "oracle")
 
 
 def test_emu_bounds_refined_one_level_down(emu, oracle):

@@ -707,16 +707,6 @@ def test_dense_sum_equals_sparse_path(hip, oracle):
         device.debug_set("dense_rows", 0)
         sparse = dist.hip_calibrate(buf, 10, flags=256, **kw)
         assert sum_path() == "sparse"
-        # the exception store (rm_xstore.h: the default for a dense selection), 1 / 2 / 4 waves per tile; then an overflowing one
-        for nw in (0, 1, 2, 4):
-            device.debug_set("xs_waves", nw)
-            assert torch.equal(dist.hip_calibrate(buf, 10, flags=128, **kw), sparse), (dt, T, H, W, L, S, "exception store", nw)
-            assert sum_path() == "dense"
-        device.debug_set("xs_waves", 0)
-        device.debug_set("xs_budget_words", 5000)
-        assert torch.equal(dist.hip_calibrate(buf, 10, flags=128, **kw), sparse), (dt, T, H, W, L, S, "exception store overflow")
-        device.debug_set("xs_budget_words", 0)
-        device.debug_set("xs", 0)                # ... and the store-less kernels it stands in front of
         for rows in (0, 16, 32, 64):
             device.debug_set("dense_rows", rows)
             assert torch.equal(dist.hip_calibrate(buf, 10, flags=128, **kw), sparse), (dt, T, H, W, L, S, rows)
@@ -746,13 +736,10 @@ def test_dense_sum_equals_sparse_path(hip, oracle):
             device.debug_set("dense_general", 0)
         device.debug_set("dense_rows", 0)
         # an 8-slot value store (RM_FLAG_TINY_STORE) overflows: the dense kernel takes over inside the same call, asked for or not
-        for xs in (0, 1):
-            device.debug_set("xs", xs)
-            for fl in (4, 4 | 256):
-                assert torch.equal(dist.hip_calibrate(buf, 10, flags=fl, **kw), sparse), (dt, T, H, W, L, S, "store overflow", fl, xs)
-                assert sum_path() == "dense"
+        for fl in (4, 4 | 256):
+            assert torch.equal(dist.hip_calibrate(buf, 10, flags=fl, **kw), sparse), (dt, T, H, W, L, S, "store overflow", fl)
+            assert sum_path() == "dense"
     device.debug_set("dense_rows", 0)
-    device.debug_set("xs", 1)
     # config Q: dense by itself, on the FIRST call of the geometry (a fresh library context: nothing is remembered between calls)
     T, H, W, L, S = 128, 720, 1280, 4, 2
     buf = torch.from_numpy(synth.synth_breathing(T, H, W, seed=1234)).cuda()
@@ -784,52 +771,30 @@ def test_dense_sum_equals_sparse_path(hip, oracle):
     assert torch.equal(dist.hip_calibrate(buf, 10), a) and sum_path() == "dense"
     device.debug_set("store_slots", 0)
     assert torch.equal(dist.hip_calibrate(buf, 10), a) and sum_path() == "sparse"
-    # the store-less passes (rm_tile_eval.h): kept pairs evaluated where they are summed -- whole tiles or half tiles, same bits
+    # the store-less passes (rm_tile_eval.h): kept pairs evaluated where they are summed, same bits
     device.debug_set("collapse_fused", 1)
     assert torch.equal(dist.hip_calibrate(buf, 10), a) and sum_path() == "fused"      # k_dense_sum_t
-    device.debug_set("dense_tiles", 0)                                                # k_tile_sum
-    for half in (-1, 0, 1):
-        device.debug_set("tile_sum_half", half)
-        assert torch.equal(dist.hip_calibrate(buf, 10), a) and sum_path() == "fused", half
-        assert torch.equal(dist.hip_calibrate(buf, 10, flags=1), a), ("no_prune", half)
-    device.debug_set("tile_sum_half", -1)
-    device.debug_set("dense_tiles", 1)
     device.debug_set("collapse_fused", 0)
-    # ... which are also what stands in for an overflowing value store at skip >= 3 (k_tile_sum behind the sparse kernel)
+    # ... which are also what stands in for an overflowing value store at skip >= 3 (k_dense_sum_t behind the sparse kernel)
     device.debug_set("store_slots", 1000)
     assert torch.equal(dist.hip_calibrate(buf, 10), a) and sum_path() == "dense"
     device.debug_set("store_slots", 0)
 
 
-def test_exception_store_few_and_many_exceptions(hip, oracle):
-    """rm_xstore.h on the streams it was built for: the 720p x 128 breathing video at skip 2 (0.6 % of the values below top: the
-    exceptions travel with the record headers) and full-frame noise at 1080p, skip 4, against the store-less kernels (xs = 0) and
-    the value-store path, bit for bit; temporal thresholds from 0.02 to 1.0 (no exceptions at all .. everything an exception); the
-    ROI of the default path is the oracle's (test_config_q_720p_full_size_vs_oracle)."""
+def test_dense_selection_720p_automatic_equals_forced_and_store_path(hip, oracle):
+    """The 720p x 128 breathing video at skip 2 (0.6 % of the values below top) at temporal thresholds from 0.0 to 1.0 (nothing ..
+    everything below top): the automatic choice equals the forced dense kernel (flags = 128) bit for bit, and the value-store path
+    (flags = 256) equals the automatic choice; the ROI of the default path is the oracle's
+    (test_config_q_720p_full_size_vs_oracle)."""
     import torch
-    from respmon_amd import device, dist, synth
+    from respmon_amd import dist, synth
     T, H, W, L, S = 128, 720, 1280, 4, 2
     buf = torch.from_numpy(synth.synth_breathing(T, H, W, seed=1234)).cuda()
     for thr in (0.7, 0.02, 0.3, 1.0, 0.0):
         kw = dict(pyramid_levels=L, skip_levels_at_top=S, temporal_threshold=thr)
-        device.debug_set("xs", 0)
         want = dist.hip_calibrate(buf, 10, flags=128, **kw)
-        device.debug_set("xs", 1)
-        for nw in (0, 1, 2):
-            device.debug_set("xs_waves", nw)
-            assert torch.equal(dist.hip_calibrate(buf, 10, flags=128, **kw), want), (thr, nw)
-        device.debug_set("xs_waves", 0)
         assert torch.equal(dist.hip_calibrate(buf, 10, **kw), want), (thr, "automatic")
     assert torch.equal(dist.hip_calibrate(buf, 10, flags=256, pyramid_levels=L, skip_levels_at_top=S), dist.hip_calibrate(buf, 10, pyramid_levels=L, skip_levels_at_top=S))
-    del buf
-    buf = torch.from_numpy(synth.synth_noise_only(64, 1080, 1920)).cuda()
-    device.debug_set("xs", 0)
-    want = dist.hip_calibrate(buf, 10, flags=128)
-    device.debug_set("xs", 1)
-    assert torch.equal(dist.hip_calibrate(buf, 10, flags=128), want)
-    device.debug_set("xs_budget_words", 200000)          # overflows: k_dense_sum_t behind k_xs_sum
-    assert torch.equal(dist.hip_calibrate(buf, 10, flags=128), want)
-    device.debug_set("xs_budget_words", 0)
 
 
 def test_bounds_refined_one_level_down_behind_a_dense_selection(hip, oracle):
@@ -871,8 +836,9 @@ def test_bounds_refined_one_level_down_behind_a_dense_selection(hip, oracle):
 
 
 def test_fused_collapse_equals_store_path(hip, oracle):
-    """rm_tile_eval.h against the selection / value-store path (flags=256), bit for bit: skip 1..4, every frame dtype, ragged sizes,
-    whole-tile and half-tile work items, exhaustive evaluation; plus the oracle's ROI on a breathing video."""
+    """rm_tile_eval.h (k_eval_pairs_fast + k_masked_sum_tiles; k_eval_c + k_dense_sum_t) against the generic selection / value-store
+    path (k_eval_pairs + k_masked_sum_tiles, flags=256), bit for bit: skip 1..4, every frame dtype, ragged sizes, pruned and
+    exhaustive evaluation; plus the oracle's ROI on a breathing video."""
     import torch
     from respmon_amd import device, dist, synth
     rng = np.random.default_rng(23)
@@ -886,30 +852,15 @@ def test_fused_collapse_equals_store_path(hip, oracle):
             buf = torch.from_numpy(v).cuda()
             kw = dict(pyramid_levels=L, skip_levels_at_top=S)
             device.debug_set("collapse_fused", 0)
-            device.debug_set("eval_fast", 0)         # the generic chain in LDS (k_eval_pairs): the reference of both newer forms
-            device.debug_set("sum_sym", 0)           # ... and the sum that fetches every visit of a frame (k_masked_sum_tiles)
-            device.debug_set("sum_rows", 0)
+            device.debug_set("eval_fast", 0)         # the generic chain in LDS (k_eval_pairs) + k_masked_sum_tiles: the reference of the newer forms
             store = dist.hip_calibrate(buf, 10, flags=256, **kw)
-            device.debug_set("sum_rows", 1)          # one wave per (tile, row), unique frames staged by LDS-DMA (k_masked_sum_rows)
-            assert torch.equal(dist.hip_calibrate(buf, 10, flags=256, **kw), store), (dt, T, H, W, L, S, "k_masked_sum_rows")
-            device.debug_set("sum_rows", 0)
-            device.debug_set("sum_sym", 1)           # unique frames loaded once, added on the way up and down (k_masked_sum_sym)
-            assert torch.equal(dist.hip_calibrate(buf, 10, flags=256, **kw), store), (dt, T, H, W, L, S, "k_masked_sum_sym")
-            device.debug_set("sum_sym", 0)
             device.debug_set("eval_fast", 1)         # the same flat pass with the wave-private evaluator (k_eval_pairs_fast)
             assert torch.equal(dist.hip_calibrate(buf, 10, flags=256, **kw), store), (dt, T, H, W, L, S, "k_eval_pairs_fast")
             assert torch.equal(dist.hip_calibrate(buf, 10, flags=256 | 1, **kw), store), (dt, T, H, W, L, S, "k_eval_pairs_fast, no_prune")
-            device.debug_set("collapse_fused", 1)
-            device.debug_set("dense_tiles", 1)       # one wave per tile, frame after frame (k_dense_sum_t)
+            device.debug_set("collapse_fused", 1)    # one wave per tile, frame after frame (k_eval_c + k_dense_sum_t)
             assert torch.equal(dist.hip_calibrate(buf, 10, **kw), store), (dt, T, H, W, L, S, "k_dense_sum_t")
             assert torch.equal(dist.hip_calibrate(buf, 10, flags=1, **kw), store), (dt, T, H, W, L, S, "k_dense_sum_t, no_prune")
-            device.debug_set("dense_tiles", 0)       # rounds of sixteen waves per tile (k_tile_sum)
-            for half in (0, 1, -1):
-                device.debug_set("tile_sum_half", half)
-                assert torch.equal(dist.hip_calibrate(buf, 10, **kw), store), (dt, T, H, W, L, S, half)
-            assert torch.equal(dist.hip_calibrate(buf, 10, flags=1, **kw), store), (dt, T, H, W, L, S, "no_prune")
         device.debug_set("collapse_fused", 1)
-        device.debug_set("sum_rows", 0)
         v8 = synth.synth_breathing(64, 270, 480, seed=5)
         fr = oracle.uint8_to_float(v8)
         buf = torch.from_numpy(fr).cuda()
@@ -922,11 +873,7 @@ def test_fused_collapse_equals_store_path(hip, oracle):
             assert dist.hip_heatmap_to_roi(heat, 20) == oracle.locate(fr, 10, pyramid_levels=L, skip_levels_at_top=S)
     finally:
         device.debug_set("collapse_fused", 0)
-        device.debug_set("tile_sum_half", -1)
         device.debug_set("eval_fast", 1)
-        device.debug_set("sum_sym", 0)
-        device.debug_set("sum_rows", 0)
-        device.debug_set("dense_tiles", 1)
 
 
 def test_filter_first_per_level_equals_fused(hip):
