@@ -25,7 +25,9 @@ extern "C" {
  * "exchange_dense" changes which collective a step issues: set it identically on EVERY rank of a communicator.
  * "flow_clip_bytes" n lowers the workspace cap of one chunk of rm_flow_clip and rm_flow_multi_clip (0: 256 MiB), so that a test splits
  * a small clip into several chunks: a chunk holds max(1, n / slot - 1) frames, slot = 5 bytes per pixel of every LK pyramid level of
- * the ROI -- for rm_flow_multi_clip the sum of that over the subjects that still have points. */
+ * the ROI -- for rm_flow_multi_clip the sum of that over the subjects that still have points.
+ * "stream_frames" n: frames per internal chunk of rm_stream_push (0: by its workspace cap of 256 MiB, at most 256), so that a test
+ * reaches the split with a handful of frames. */
 int rm_debug_set(rm_ctx *ctx, const char *key, long long value);
 
 /* counters of the last rm_calibrate on this context: out_host[0] = (frame, tile) pairs, [1] = pairs evaluated at full resolution

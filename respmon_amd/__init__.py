@@ -13,7 +13,7 @@ def __getattr__(name):
     if name == "SubjectTracker":
         from .subjects import SubjectTracker
         return SubjectTracker
-    if name in ("transforms", "pyramid", "base", "device", "synth", "dist", "subjects", "measure"):
+    if name in ("transforms", "pyramid", "base", "device", "synth", "dist", "subjects", "measure", "live", "window"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

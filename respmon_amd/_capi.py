@@ -64,6 +64,7 @@ SIGNATURES = {
     "rm_temporal_operator": (_i, [_i, _d, _d, _d, _vp, _c.POINTER(_i), _c.POINTER(_i)]),
     "rm_time_average": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp]),
     "rm_lfilter": (_i, [_vp, _vp, _i, _sz, _vp, _vp, _i, _d, _vp, _vp]),
+    "rm_sosfilt": (_i, [_vp, _vp, _i, _sz, _vp, _i, _vp, _d, _vp, _vp]),
     "rm_threshold_mask": (_i, [_vp, _vp, _sz, _d, _vp, _vp, _vp]),
     "rm_eulerian_magnification_bandpass": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _d, _vp, _vp, _vp, _vp]),
     "rm_magnify": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _vp, _i, _vp]),
@@ -94,6 +95,11 @@ SIGNATURES = {
     "rm_window_locate": (_i, [_vp, _vp, _d, _d, _d, _d, _d, _i, _vp, _vp]),
     "rm_window_locate_multi": (_i, [_vp, _vp, _d, _d, _d, _d, _d, _i, _i, _d, _vp, _vp, _c.POINTER(_i), _vp]),
     "rm_debug_window_rows": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "rm_stream_create": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _d, _c.POINTER(_vp)]),
+    "rm_stream_destroy": (_i, [_vp]),
+    "rm_stream_reset": (_i, [_vp, _vp]),
+    "rm_stream_info": (_i, [_vp, _c.POINTER(_c.c_longlong), _c.POINTER(_sz), _c.POINTER(_sz)]),
+    "rm_stream_push": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "rm_roi_mean": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_roi_to_uint8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_good_features_to_track": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp]),

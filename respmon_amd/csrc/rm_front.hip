@@ -125,6 +125,71 @@ int front_pyramid(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int 
     return RM_OK;
 }
 
+// collapse of the band-passed levels L-2 .. S of `rows` frames, bp[rows, NP] (pyramid.py:51-57; the coarsest level is zeros:
+// 0 + x == x) -> out.cS, a contiguous [rows, h_S, w_S] array for the full-resolution passes.  The part of front_filter behind the
+// temporal filter (rows = the unique frames there); rm_stream_push runs it on the frames of a chunk (bounds = false: no tile bounds,
+// nothing selects among its frames).  state_fresh: ctx->d_state was reset by front_pyramid just now.  Reduces into ctx->d_state.
+int collapse_levels(rm_ctx *ctx, double *bp, int rows, const PyrGeom &pg, bool state_fresh, bool bounds, SmallLevels &out, hipStream_t s)
+{
+    const std::vector<int> &h = pg.h, &w = pg.w;
+    const int L = pg.L, S = pg.S, Th = rows;
+    const size_t NP = pg.NP;
+    out.h = pg.h; out.w = pg.w; out.S = S; out.all_zero = false;
+    const double *c = bp + pg.off[L - 2];
+    if (L - 2 == S) {
+        // single filtered level: NP == h_S*w_S, bp_all is already C_S
+    } else if (pg.fuse_small) {
+        double *dst = nullptr;
+        RM_TRY(ws(ctx, "cS", (size_t)Th * h[S] * w[S], &dst));
+        const size_t shmem = NP * sizeof(double);
+        if (shmem > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void *)k_small_collapse<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+        // when the row-extrema table of a frame fits beside its small pyramid, the tile bounds of the collapse passes
+        // are taken here, from the LDS copy of C_S (k_small_collapse_bounds)
+        ChainGeom cg;
+        SmallLevels probe; probe.h = pg.h; probe.w = pg.w; probe.S = S;
+        const bool geom_ok = S >= 1 && S < MAX_CHAIN && make_geom(probe, cg) == RM_OK;
+        const size_t tbl = geom_ok ? 2 * sizeof(double) * (size_t)h[S] * cg.tiles_x : 0;
+        const long long npairs = geom_ok ? (long long)cg.tiles_x * cg.tiles_y * Th : 0;
+        if (bounds && geom_ok && shmem + tbl <= 150 * 1024 && npairs < (1ll << 31) && !ctx->dbg.no_fused_bounds) {
+            double *lo = nullptr, *hi = nullptr;
+            int *sel_cnt = nullptr;
+            RM_TRY(ws(ctx, "tile_lo", (size_t)npairs, &lo));
+            RM_TRY(ws(ctx, "tile_hi", (size_t)npairs, &hi));
+            RM_TRY(ws(ctx, "sel_cnt", (size_t)cg.tiles_x * cg.tiles_y, &sel_cnt));
+            if (!state_fresh) {   // the lap buffer did not come from front_pyramid on this context just now
+                hipLaunchKernelGGL(k_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, ctx->d_state);
+                LAUNCH_CHECK();
+            }
+            const size_t sh2 = shmem + tbl;
+            if (sh2 > 64 * 1024)
+                HIP_TRY(hipFuncSetAttribute((const void *)k_small_collapse_bounds<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh2));
+            hipLaunchKernelGGL(k_small_collapse_bounds<>, dim3(Th), dim3(SMALL_NT), sh2, s, (const double *)bp, pg.sg, dst, ctx->d_state, cg,
+                               cg.tiles_x * cg.tiles_y, lo, hi, sel_cnt);
+            out.state_ready = true; out.bounds_ready = true;
+        } else {
+            hipLaunchKernelGGL(k_small_collapse<>, dim3(Th), dim3(SMALL_NT), shmem, s, (const double *)bp, pg.sg, dst, ctx->d_state);
+            out.state_ready = true;
+        }
+        LAUNCH_CHECK();
+        c = dst;
+    } else {
+        size_t c_fs = NP;
+        for (int l = L - 3; l >= S; --l) {
+            double *dst = bp + pg.off[l];
+            size_t dst_fs = NP;
+            if (l == S) {
+                RM_TRY(ws(ctx, "cS", (size_t)Th * h[S] * w[S], &dst));
+                dst_fs = (size_t)h[S] * w[S];
+            }
+            RM_TRY(launch_pyr_up(c, Th, h[l + 1], w[l + 1], dst, h[l], w[l], 2, bp + pg.off[l], s, c_fs, dst_fs, NP));
+            c = dst; c_fs = dst_fs;
+        }
+    }
+    out.cS = c;
+    return RM_OK;
+}
+
 int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, double fps, double fmin, double fmax, double amp,
                         SmallLevels &out, hipStream_t s, int head)
 {
@@ -217,61 +282,7 @@ int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, doubl
     }
     // temporal band-pass of every level at once (transforms.py:162,169)
     RM_TRY(launch_temporal(ctx, lap, T, NP, op, amp, bp, s, nullptr, false, head));
-    // collapse of the band-passed levels L-2 .. S (pyramid.py:51-57; the coarsest level is zeros: 0 + x == x);
-    // the result is a contiguous [Th,h_S,w_S] array for the full-resolution passes
-    const double *c = bp + pg.off[L - 2];
-    if (L - 2 == S) {
-        // single filtered level: NP == h_S*w_S, bp_all is already C_S
-    } else if (pg.fuse_small) {
-        double *dst = nullptr;
-        RM_TRY(ws(ctx, "cS", (size_t)Th * h[S] * w[S], &dst));
-        const size_t shmem = NP * sizeof(double);
-        if (shmem > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void *)k_small_collapse<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        // when the row-extrema table of a frame fits beside its small pyramid, the tile bounds of the collapse passes
-        // are taken here, from the LDS copy of C_S (k_small_collapse_bounds)
-        ChainGeom cg;
-        SmallLevels probe; probe.h = pg.h; probe.w = pg.w; probe.S = S;
-        const bool geom_ok = S >= 1 && S < MAX_CHAIN && make_geom(probe, cg) == RM_OK;
-        const size_t tbl = geom_ok ? 2 * sizeof(double) * (size_t)h[S] * cg.tiles_x : 0;
-        const long long npairs = geom_ok ? (long long)cg.tiles_x * cg.tiles_y * Th : 0;
-        if (geom_ok && shmem + tbl <= 150 * 1024 && npairs < (1ll << 31) && !ctx->dbg.no_fused_bounds) {
-            double *lo = nullptr, *hi = nullptr;
-            int *sel_cnt = nullptr;
-            RM_TRY(ws(ctx, "tile_lo", (size_t)npairs, &lo));
-            RM_TRY(ws(ctx, "tile_hi", (size_t)npairs, &hi));
-            RM_TRY(ws(ctx, "sel_cnt", (size_t)cg.tiles_x * cg.tiles_y, &sel_cnt));
-            if (!state_fresh) {   // the lap buffer did not come from front_pyramid on this context just now
-                hipLaunchKernelGGL(k_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, ctx->d_state);
-                LAUNCH_CHECK();
-            }
-            const size_t sh2 = shmem + tbl;
-            if (sh2 > 64 * 1024)
-                HIP_TRY(hipFuncSetAttribute((const void *)k_small_collapse_bounds<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh2));
-            hipLaunchKernelGGL(k_small_collapse_bounds<>, dim3(Th), dim3(SMALL_NT), sh2, s, (const double *)bp, pg.sg, dst, ctx->d_state, cg,
-                               cg.tiles_x * cg.tiles_y, lo, hi, sel_cnt);
-            out.state_ready = true; out.bounds_ready = true;
-        } else {
-            hipLaunchKernelGGL(k_small_collapse<>, dim3(Th), dim3(SMALL_NT), shmem, s, (const double *)bp, pg.sg, dst, ctx->d_state);
-            out.state_ready = true;
-        }
-        LAUNCH_CHECK();
-        c = dst;
-    } else {
-        size_t c_fs = NP;
-        for (int l = L - 3; l >= S; --l) {
-            double *dst = bp + pg.off[l];
-            size_t dst_fs = NP;
-            if (l == S) {
-                RM_TRY(ws(ctx, "cS", (size_t)Th * h[S] * w[S], &dst));
-                dst_fs = (size_t)h[S] * w[S];
-            }
-            RM_TRY(launch_pyr_up(c, Th, h[l + 1], w[l + 1], dst, h[l], w[l], 2, bp + pg.off[l], s, c_fs, dst_fs, NP));
-            c = dst; c_fs = dst_fs;
-        }
-    }
-    out.cS = c;
-    return RM_OK;
+    return collapse_levels(ctx, bp, Th, pg, state_fresh, true, out, s);
 }
 
 int front_half(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, double fps, double fmin, double fmax,

@@ -15,6 +15,7 @@
 //   rm_motion.hip         ROI mean / crop, corners, LK, PCA; the ROI means and the LK flow of several subjects (base.py:354-407; rm_subjects.h, rm_flow_multi.h)
 //   rm_window.hip         rm_window_*: a ring of per-frame pyramid rows, relocated in place          (base.py:409-513 without the refill)
 //   rm_magnify.hip        rm_magnify, rm_magnify_bgr: frames + band-passed motion in one pass            (transforms.py:170, 181; rm_magnify.h)
+//   rm_stream.hip         rm_sosfilt, rm_stream_*: the causal band-pass in second-order sections with carried state, a live stream magnified chunk by chunk (rm_stream_kernels.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
 // Every kernel header is included by every unit; non-template kernels are `static`, so a unit generates code only for the kernels
 // it launches.
@@ -126,6 +127,7 @@ struct DebugKnobs {
     int dense_t_low = -1;         // k_dense_sum_t (TileEval) at skip <= 2 instead of k_dense_sum_w / wf: 1 always, 0 never, -1 on large frames
     long long store_default_slots = 0;   // > 0: slots the value store starts with before any selection has made it grow (default 16 384)
     long long store_slots = 0;    // > 0: capacity of the value store in (tile, frame) slots (forces the overflow path)
+    int stream_frames = 0;        // > 0: frames per internal chunk of rm_stream_push (default: by the workspace cap, at most 256)
     long long flow_clip_bytes = 0;   // > 0: workspace cap of one chunk of rm_flow_clip / rm_flow_multi_clip (default 256 MiB): a chunk holds max(1, cap / slot - 1) frames, slot = 5 bytes per pixel of every LK pyramid level of the ROI (summed over the subjects that still have points)
 };
 
@@ -331,6 +333,7 @@ void pyr_geom(int H, int W, int levels, int skip, unsigned flags, PyrGeom &pg);
 int front_pyramid(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, const PyrGeom &pg, unsigned flags, double *lap, hipStream_t s);
 int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, double fps, double fmin, double fmax, double amp, SmallLevels &out,
                  hipStream_t s, int head = 0);   // head > 0: lap is a ring of T rows (launch_temporal); nothing behind the temporal filter knows
+int collapse_levels(rm_ctx *ctx, double *bp, int rows, const PyrGeom &pg, bool state_fresh, bool bounds, SmallLevels &out, hipStream_t s);
 int front_half(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, double fps, double fmin, double fmax, double amp, int levels,
                int skip, unsigned flags, SmallLevels &out, hipStream_t s);
 int make_geom(const SmallLevels &sl, rm::ChainGeom &g);
@@ -344,6 +347,9 @@ int collapse_sum(rm_ctx *ctx, const CollapsePlan &cp, double thr, double *heat_s
 int zero_result(rm_ctx *ctx, size_t npix, double *heat, double *minmax_host, hipStream_t s);
 int calibrate_impl(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, double fps, double fmin, double fmax, double amp, int levels,
                    int skip, double thr, unsigned flags, double *heat, double *minmax_host, void *stream, CollapsePlan *plan_out);
+
+// ---- rm_magnify.hip: the sum kernels with a row of C_S per frame (rm_stream.hip)
+int magnify_rows(rm_ctx *ctx, const void *frames, int dtype, int n, int H, int W, const SmallLevels &sl, void *out, int out_dtype, hipStream_t s);
 
 // ---- rm_roi.hip: the ROI stage in two halves (device launches, then -- once they have been waited for -- the host contour stage)
 int roi_launch(rm_ctx *ctx, const double *heat, int H, int W, int threshold, uint8_t *avg_u8, uint8_t *binary, void *stream, bool have_minmax,

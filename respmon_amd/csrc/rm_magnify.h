@@ -206,7 +206,9 @@ __device__ __forceinline__ void mag_store(Tout *p, int nvalid, const MagIn<Tin, 
 
 // grid: ntiles * ceil(Th / MAG_FC) single-wave workgroups, block = chunk * ntiles + tile (neighbours in the grid work on neighbouring
 // tiles of the same frames); dynamic LDS: MAG_LDS_DOUBLES doubles.  vec: rows and base addresses allow the aligned whole-chunk accesses.
-template <int S, typename Tin, typename Tout>
+// SYM = 1: the band-passed signal is even in time (the FFT operator of rm_magnify), C_S holds the unique frames.  SYM = 0: every frame
+// owns its row of C_S (Th = T; the causal filter of rm_stream_push): no second served frame, one frame tile in flight instead of two.
+template <int S, typename Tin, typename Tout, int SYM = 1>
 __global__ __launch_bounds__(64) void k_magnify(const double *cS, ChainGeom g, int T, int ntiles, const Tin *frames, Tout *out, int vec)
 {
     using F = TileFoot<S>;
@@ -216,7 +218,7 @@ __global__ __launch_bounds__(64) void k_magnify(const double *cS, ChainGeom g, i
     const int lane = threadIdx.x;
     const int tile = (int)blockIdx.x % ntiles, chunk = (int)blockIdx.x / ntiles;
     const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
-    const int Th = sym_frames(T);
+    const int Th = SYM ? sym_frames(T) : T;
     const int u0 = chunk * MAG_FC, u1 = min(Th, u0 + MAG_FC);
     const int H0 = g.h[0], W0 = g.w[0];
     const size_t fs = (size_t)g.h[S] * g.w[S], npix = (size_t)H0 * W0;
@@ -233,21 +235,24 @@ __global__ __launch_bounds__(64) void k_magnify(const double *cS, ChainGeom g, i
         px_off[p] = (size_t)min(y, H0 - 1) * W0 + min(x, W0 - 1);
     }
     for (int u = u0; u < u1; ++u) {
-        const int t2 = (u >= 1 && 2 * u != T) ? T - u : -1;   // (uniform) the second frame this evaluation serves
+        const int t2 = (SYM && u >= 1 && 2 * u != T) ? T - u : -1;   // (uniform) the second frame this evaluation serves
         const double *src = cS + (size_t)u * fs;
         double stg[F::PF];
 #pragma unroll
         for (int p = 0; p < F::PF; ++p) stg[p] = src[ts.off_g[p]];
         // the frame tiles travel while the evaluation runs
-        MagIn<Tin, Tout> in_a[G::NP], in_b[G::NP];
+        MagIn<Tin, Tout> in_a[G::NP], in_b[SYM ? G::NP : 1];
         const Tin *fa = frames + (size_t)u * npix, *fb = frames + (size_t)(t2 >= 0 ? t2 : u) * npix;
 #pragma unroll
         for (int p = 0; p < G::NP; ++p) {
             if (vec) {
-                if (nvalid[p] > 0) { mag_load<Tin, Tout, true>(fa + px_off[p], G::V, in_a[p]); if (t2 >= 0) mag_load<Tin, Tout, true>(fb + px_off[p], G::V, in_b[p]); }
+                if (nvalid[p] > 0) {
+                    mag_load<Tin, Tout, true>(fa + px_off[p], G::V, in_a[p]);
+                    if constexpr (SYM) if (t2 >= 0) mag_load<Tin, Tout, true>(fb + px_off[p], G::V, in_b[p]);
+                }
             } else {
                 mag_load<Tin, Tout, false>(fa + px_off[p], nvalid[p], in_a[p]);
-                if (t2 >= 0) mag_load<Tin, Tout, false>(fb + px_off[p], nvalid[p], in_b[p]);
+                if constexpr (SYM) if (t2 >= 0) mag_load<Tin, Tout, false>(fb + px_off[p], nvalid[p], in_b[p]);
             }
         }
         wave_sync();   // the previous frame's reads of the slice are behind us
@@ -272,10 +277,10 @@ __global__ __launch_bounds__(64) void k_magnify(const double *cS, ChainGeom g, i
             if (nvalid[p] > 0) {
                 if (vec) {
                     mag_store<Tin, Tout, true>(out + (size_t)u * npix + px_off[p], G::V, in_a[p], raw);
-                    if (t2 >= 0) mag_store<Tin, Tout, true>(out + (size_t)t2 * npix + px_off[p], G::V, in_b[p], raw);
+                    if constexpr (SYM) if (t2 >= 0) mag_store<Tin, Tout, true>(out + (size_t)t2 * npix + px_off[p], G::V, in_b[p], raw);
                 } else {
                     mag_store<Tin, Tout, false>(out + (size_t)u * npix + px_off[p], nvalid[p], in_a[p], raw);
-                    if (t2 >= 0) mag_store<Tin, Tout, false>(out + (size_t)t2 * npix + px_off[p], nvalid[p], in_b[p], raw);
+                    if constexpr (SYM) if (t2 >= 0) mag_store<Tin, Tout, false>(out + (size_t)t2 * npix + px_off[p], nvalid[p], in_b[p], raw);
                 }
             }
         }
@@ -283,13 +288,13 @@ __global__ __launch_bounds__(64) void k_magnify(const double *cS, ChainGeom g, i
 }
 
 // out[t, p] = convert(f[t, p] + raw[sym_frame(t), p]) (colour: per channel of f[t, p], the header of this file); raw: the unique frames [T / 2 + 1][npix], or null where nothing is filtered (raw == 0).
-// blockIdx.y = t.
-template <typename Tin, typename Tout>
+// SYM = 0: raw is [T][npix], a row per frame.  blockIdx.y = t.
+template <typename Tin, typename Tout, int SYM = 1>
 __global__ __launch_bounds__(256) void k_magnify_plain(const Tin *frames, const double *raw, int T, size_t npix, Tout *out)
 {
     const int t = (int)blockIdx.y;
     const Tin *f = frames + (size_t)t * npix;
-    const double *r = raw ? raw + (size_t)sym_frame(t, T) * npix : nullptr;
+    const double *r = raw ? raw + (size_t)(SYM ? sym_frame(t, T) : t) * npix : nullptr;
     Tout *o = out + (size_t)t * npix;
     for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (size_t)gridDim.x * 256) {
         const typename MagPx<Tin>::E *e = reinterpret_cast<const typename MagPx<Tin>::E *>(f + p);

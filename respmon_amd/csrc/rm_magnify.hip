@@ -14,66 +14,67 @@ struct MagCall {
     hipStream_t s;
 };
 
-template <int S, typename Tin, typename Tout>
+// SYM = 1: rm_magnify / rm_magnify_bgr (cS / raw hold the unique frames of a signal even in time); SYM = 0: a row per frame (magnify_rows)
+template <int S, typename Tin, typename Tout, int SYM>
 int launch_fused(const MagCall &c, const double *cS, const ChainGeom &g)
 {
     using G = MagGeom<Tin, Tout>;
-    const int ntiles = g.tiles_x * g.tiles_y, nchunks = (sym_frames(c.T) + MAG_FC - 1) / MAG_FC;
+    const int ntiles = g.tiles_x * g.tiles_y, nchunks = ((SYM ? sym_frames(c.T) : c.T) + MAG_FC - 1) / MAG_FC;
     const int vec = ((((uintptr_t)c.frames | (uintptr_t)c.out) & 15) == 0 && c.W % G::V == 0) ? 1 : 0;
-    hipLaunchKernelGGL((k_magnify<S, Tin, Tout>), dim3((unsigned)(ntiles * nchunks)), dim3(64), sizeof(double) * MAG_LDS_DOUBLES, c.s, cS, g, c.T, ntiles,
+    hipLaunchKernelGGL((k_magnify<S, Tin, Tout, SYM>), dim3((unsigned)(ntiles * nchunks)), dim3(64), sizeof(double) * MAG_LDS_DOUBLES, c.s, cS, g, c.T, ntiles,
                        (const Tin *)c.frames, (Tout *)c.out, vec);
     LAUNCH_CHECK();
     return RM_OK;
 }
 
-template <typename Tin, typename Tout>
+template <typename Tin, typename Tout, int SYM = 1>
 int launch_any(const MagCall &c, const double *cS, const ChainGeom *g, const double *raw)
 {
     if (g) {
         switch (g->S) {
-        case 1: return launch_fused<1, Tin, Tout>(c, cS, *g);
-        case 2: return launch_fused<2, Tin, Tout>(c, cS, *g);
-        case 3: return launch_fused<3, Tin, Tout>(c, cS, *g);
-        default: return launch_fused<4, Tin, Tout>(c, cS, *g);
+        case 1: return launch_fused<1, Tin, Tout, SYM>(c, cS, *g);
+        case 2: return launch_fused<2, Tin, Tout, SYM>(c, cS, *g);
+        case 3: return launch_fused<3, Tin, Tout, SYM>(c, cS, *g);
+        default: return launch_fused<4, Tin, Tout, SYM>(c, cS, *g);
         }
     }
     const size_t npix = (size_t)c.H * c.W;
-    hipLaunchKernelGGL((k_magnify_plain<Tin, Tout>), dim3(nblk(npix, 256, 4096), (unsigned)c.T), dim3(256), 0, c.s, (const Tin *)c.frames, raw, c.T, npix,
+    hipLaunchKernelGGL((k_magnify_plain<Tin, Tout, SYM>), dim3(nblk(npix, 256, 4096), (unsigned)c.T), dim3(256), 0, c.s, (const Tin *)c.frames, raw, c.T, npix,
                        (Tout *)c.out);
     LAUNCH_CHECK();
     return RM_OK;
 }
 
-template <typename Tin>
+template <typename Tin, int SYM = 1>
 int launch_out(const MagCall &c, int out_dtype, const double *cS, const ChainGeom *g, const double *raw)
 {
     switch (out_dtype) {
-    case RM_U8: return launch_any<Tin, uint8_t>(c, cS, g, raw);
-    case RM_F32: return launch_any<Tin, float>(c, cS, g, raw);
-    default: return launch_any<Tin, double>(c, cS, g, raw);
+    case RM_U8: return launch_any<Tin, uint8_t, SYM>(c, cS, g, raw);
+    case RM_F32: return launch_any<Tin, float, SYM>(c, cS, g, raw);
+    default: return launch_any<Tin, double, SYM>(c, cS, g, raw);
     }
 }
 
+template <int SYM = 1>
 int launch_in(const MagCall &c, int dtype, int out_dtype, const double *cS, const ChainGeom *g, const double *raw)
 {
     switch (dtype) {
-    case RM_U8: return launch_out<uint8_t>(c, out_dtype, cS, g, raw);
-    case RM_F16: return launch_out<__half>(c, out_dtype, cS, g, raw);
-    case RM_F32: return launch_out<float>(c, out_dtype, cS, g, raw);
-    case RM_F64: return launch_out<double>(c, out_dtype, cS, g, raw);
-    default: return launch_out<bgr8_t>(c, out_dtype, cS, g, raw);
+    case RM_U8: return launch_out<uint8_t, SYM>(c, out_dtype, cS, g, raw);
+    case RM_F16: return launch_out<__half, SYM>(c, out_dtype, cS, g, raw);
+    case RM_F32: return launch_out<float, SYM>(c, out_dtype, cS, g, raw);
+    case RM_F64: return launch_out<double, SYM>(c, out_dtype, cS, g, raw);
+    default: return launch_out<bgr8_t, SYM>(c, out_dtype, cS, g, raw);
     }
 }
 
-// behind front_half(): launch(cS, geometry, raw) with nothing filtered (all null: raw == 0), the level-S signal and the geometry of
-// the fused kernel (1 <= S <= 4 where TileEval applies), or the materialised unique frames of raw
+// behind the collapse to level S, `rows` frames of C_S (the unique frames of rm_magnify, every frame of a stream chunk): launch(cS,
+// geometry, raw) with nothing filtered (all null: raw == 0), the level-S signal and the geometry of the fused kernel (1 <= S <= 4 where
+// TileEval applies), or the materialised rows of raw
 template <typename Launch>
-int magnify_dispatch(rm_ctx *ctx, const MagCall &c, int dtype, double fps, double fmin, double fmax, double amp, int levels, int skip, Launch launch)
+int magnify_tail(rm_ctx *ctx, const MagCall &c, const SmallLevels &sl, int rows, Launch launch)
 {
-    SmallLevels sl;
-    RM_TRY(front_half(ctx, c.frames, dtype, c.T, c.H, c.W, fps, fmin, fmax, amp, levels, skip, 0, sl, c.s));
     if (sl.all_zero) return launch(nullptr, nullptr, nullptr);   // nothing is filtered: raw == 0
-    const int Th = sym_frames(c.T);
+    const int Th = rows;
     if (sl.S >= 1 && sl.S <= 4) {
         ChainGeom g;
         RM_TRY(make_geom(sl, g));
@@ -91,6 +92,14 @@ int magnify_dispatch(rm_ctx *ctx, const MagCall &c, int dtype, double fps, doubl
     return launch(nullptr, nullptr, cur);
 }
 
+template <typename Launch>
+int magnify_dispatch(rm_ctx *ctx, const MagCall &c, int dtype, double fps, double fmin, double fmax, double amp, int levels, int skip, Launch launch)
+{
+    SmallLevels sl;
+    RM_TRY(front_half(ctx, c.frames, dtype, c.T, c.H, c.W, fps, fmin, fmax, amp, levels, skip, 0, sl, c.s));
+    return magnify_tail(ctx, c, sl, sym_frames(c.T), launch);
+}
+
 bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
 {
     const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
@@ -98,6 +107,16 @@ bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
 }
 
 }  // namespace
+
+// out[t] = convert(f[t] + pyrUp^S(C_S[t])) for the n frames of a stream chunk, C_S[t] = sl.cS + t * h_S * w_S (rm_stream.hip): the
+// dispatch of magnify_dispatch with a row of C_S per frame.  out_dtype RM_BGR8: the colour rule of rm_magnify_bgr (dtype RM_BGR8 only).
+int magnify_rows(rm_ctx *ctx, const void *frames, int dtype, int n, int H, int W, const SmallLevels &sl, void *out, int out_dtype, hipStream_t s)
+{
+    const MagCall c{frames, out, n, H, W, s};
+    if (out_dtype == RM_BGR8)
+        return magnify_tail(ctx, c, sl, n, [&](const double *cS, const ChainGeom *g, const double *raw) { return launch_any<bgr8_t, bgr8_t, 0>(c, cS, g, raw); });
+    return magnify_tail(ctx, c, sl, n, [&](const double *cS, const ChainGeom *g, const double *raw) { return launch_in<0>(c, dtype, out_dtype, cS, g, raw); });
+}
 
 extern "C" int rm_magnify(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, double fps, double fmin, double fmax, double amp,
                           int levels, int skip, void *out, int out_dtype, void *stream)
@@ -113,7 +132,7 @@ extern "C" int rm_magnify(rm_ctx *ctx, const void *frames, int dtype, int T, int
     RM_TRY(ctx_stream_ok(ctx, stream, __func__));
     const MagCall c{frames, out, T, H, W, (hipStream_t)stream};
     return magnify_dispatch(ctx, c, dtype, fps, fmin, fmax, amp, levels, skip,
-                            [&](const double *cS, const ChainGeom *g, const double *raw) { return launch_in(c, dtype, out_dtype, cS, g, raw); });
+                            [&](const double *cS, const ChainGeom *g, const double *raw) { return launch_in<1>(c, dtype, out_dtype, cS, g, raw); });
 }
 
 // the colour form: BGR frames in, BGR video out, the same raw onto the three channels (rm_magnify.h)

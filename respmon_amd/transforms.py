@@ -124,10 +124,58 @@ def butter_lowpass(cutoff, fs, order=5):
 def temporal_bandpass_filter(data, fps, freq_min=0.833, freq_max=1, axis=0,
                              amplification_factor=50, verbose=False, debug=''):
     """reference transforms.py:72-79: order-6 Butterworth band-pass (lfilter) along `axis`, times the
-    amplification -- the IIR alternative to temporal_bandpass_filter_fft."""
+    amplification -- the IIR alternative to temporal_bandpass_filter_fft.
+
+    The reference's `ba` form is numerically UNSTABLE at camera rates: in float64 the order-6 design has poles outside the unit
+    circle (fps 30, 0.1-0.5 Hz: largest pole 1.056, |y| reaches 1.7e19 within 2 000 samples of uniform noise in [0, 1]; fps 30,
+    0.1-1.0 Hz: 1.015 and 3e11; at fps 60 the output overflows; stable only at low rates such as fps 10, largest pole 0.986).  This
+    function keeps the reference's behaviour; temporal_bandpass_filter_sos is the same design as second-order sections (largest pole
+    0.9963 at fps 30, 0.1-0.5 Hz; |y| <= 0.29 on the same input)."""
     b, a = butter_bandpass(freq_min, freq_max, fps, order=6)
     result = butter_bandpass_filter_fast(data, b, a, axis=axis)
     result *= amplification_factor
+    if verbose:
+        print('{0}{1},{2}'.format(debug, float(result.min()), float(result.max())))
+    return result
+
+
+def butter_bandpass_sos(_lowcut, _highcut, _fs, order=6):
+    """butter_bandpass's design (transforms.py:38-44) as second-order sections [order, 6] (host, scipy)."""
+    from scipy.signal import butter
+    _nyq = 0.5 * _fs
+    return butter(order, [_lowcut / _nyq, _highcut / _nyq], btype='band', output='sos')
+
+
+def sosfilt_device(data, sos, zi=None, scale=1.0):
+    """scipy.signal.sosfilt(sos, data, axis=0) * scale on the device (rm_sosfilt: one lane per element, scipy's operation order);
+    `zi` [n_sections, 2] (scipy.signal.sosfilt_zi): every element starts at zi * data[0], the steady state of its first sample."""
+    t = device.require_gpu()
+    lib = _capi.load()
+    x = device.to_device(data, t.float64)
+    out = t.empty(x.shape, dtype=t.float64, device=x.device)
+    sos = np.ascontiguousarray(sos, dtype=np.float64)
+    z = None if zi is None else np.ascontiguousarray(zi, dtype=np.float64)
+    if sos.ndim != 2 or sos.shape[1] != 6 or (z is not None and z.shape != (sos.shape[0], 2)):
+        raise ValueError("sos must be [n_sections, 6] and zi [n_sections, 2]")
+    _capi.check(lib, lib.rm_sosfilt(device.ctx(), device.ptr(x), x.shape[0], x[0].numel(), ctypes.c_void_p(sos.ctypes.data), sos.shape[0],
+                                    None if z is None else ctypes.c_void_p(z.ctypes.data), float(scale), device.ptr(out),
+                                    device.stream_ptr()), "rm_sosfilt")
+    return device.like_input(out, data)
+
+
+def temporal_bandpass_filter_sos(data, fps, freq_min=0.833, freq_max=1, axis=0,
+                                 amplification_factor=50, verbose=False, debug=''):
+    """temporal_bandpass_filter with its order-6 Butterworth band-pass as second-order sections: scipy.signal.sosfilt(sos, data,
+    axis) * amplification, from rest.  The reference's filter signature, so eulerian_magnification_bandpass(temporal_filter_function=
+    temporal_bandpass_filter_sos) takes it; stable where the `ba` form is not (see temporal_bandpass_filter).  Videos ([T,...], axis 0)
+    run on the device (rm_sosfilt); anything else is a small host-side signal and goes to scipy, as in butter_bandpass_filter_fast."""
+    sos = butter_bandpass_sos(freq_min, freq_max, fps, order=6)
+    is_tensor = hasattr(data, "is_cuda")
+    if axis != 0 or (not is_tensor and np.ndim(data) < 2):
+        from scipy.signal import sosfilt
+        result = sosfilt(sos, data.cpu().numpy() if is_tensor else data, axis=axis) * amplification_factor
+    else:
+        result = sosfilt_device(data, sos, scale=float(amplification_factor))
     if verbose:
         print('{0}{1},{2}'.format(debug, float(result.min()), float(result.max())))
     return result

@@ -13,10 +13,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT = os.path.join(ROOT, "respmon_amd", "csrc", "build_resources.txt")
 # kernels that must hold their state in registers: the hot (VB = false) instantiations of the float64 chain and every narrow chain
 # ... and the per-clip LK tracker (rm_flow_multi.h): its wave walks all frames of a chunk, scratch would be paid once per frame and point
+# ... and the live stream (rm_stream.hip): k_sosfilt keeps the 2 x nsec state values of its element in registers over a whole call, and the
+#     SYM = 0 instances of k_magnify (one frame tile in flight) fall under the k_magnify pattern with the SYM = 1 ones
 # ... and the multi-subject ROI mean (rm_subjects.h): a workgroup per (frame, subject) pair streams its rectangle once
 MUST_NOT_SPILL = re.compile(r"^(void )?rm::k_down_chain<[^>]*, false>|^(void )?rm::k_down_chain_u8<|^(void )?rm::k_down_chain_narrow<|"
                             r"^(void )?rm::k_magnify<|^(void )?rm::k_roi_mean_multi_clip<|"
-                            r"^(void )?rm::k_lk_track_multi_clip<")
+                            r"^(void )?rm::k_lk_track_multi_clip<|^(void )?rm::k_sosfilt<")
 
 
 def demangle(names):
