@@ -20,10 +20,12 @@
 //     evaluation forms; v_min_f64 / v_max_f64 (a NaN is dropped, as the comparison folds of the other bounds kernels drop it);
 //   * at every eighth level-1 row the three tiles' extrema are folded over their 17 lanes with DPP row shifts and written --
 //     [unique frame][tile], as the other bounds kernels write them;
-//   * the extrema of the bounds go to the striped state as in k_frame_bounds_rows, and two lattice samples per wave (rm_kernels.h
+//   * the extrema of the bounds go to the striped state as in k_frame_bounds_rows, and two lattice samples per wave (rm_small_kernels.h
 //     lattice_sample: true raw values) taken where the wave met its lowest / highest C_2.
 // No LDS, no barrier.  C_2 is read once.
 #pragma once
+#include "rm_small_kernels.h"
+#include "rm_tile_eval.h"
 
 namespace rm {
 

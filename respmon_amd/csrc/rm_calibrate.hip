@@ -1,6 +1,7 @@
 // respmon_amd/csrc/rm_calibrate.hip -- rm_calibrate, the frame-sharded stages and the materialising eulerian_magnification_bandpass
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_select_kernels.h"
 
 using namespace rm;
 
@@ -11,10 +12,7 @@ int zero_result(rm_ctx *ctx, size_t npix, double *heat, double *minmax_host, hip
 {
     ctx->state_fresh = false;
     HIP_TRY(hipMemsetAsync(heat, 0, sizeof(double) * npix, s));
-    hipLaunchKernelGGL(k_heat_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, ctx->d_state);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_heat_minmax<>, dim3(1), dim3(256), 0, s, (const double *)heat, (size_t)1, ctx->d_state);
-    LAUNCH_CHECK();
+    RM_TRY(launch_heat_minmax(ctx->d_state, heat, 1, s));
     if (minmax_host) { minmax_host[0] = 0.0; minmax_host[1] = 0.0; HIP_TRY(stream_wait(s)); }
     return RM_OK;
 }
@@ -144,11 +142,9 @@ extern "C" int rm_shard_finish(rm_ctx *ctx, const double *heat_sum, int T, int H
     HIP_TRY(hipSetDevice(ctx->device));
     RM_TRY(ctx_stream_ok(ctx, stream, __func__));
     const size_t npix = (size_t)H * W;
-    hipLaunchKernelGGL(k_heat_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, ctx->d_state);
     ctx->state_fresh = false;
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_heat_avg_minmax<>, dim3(nblk(npix, 256, 256)), dim3(256), 0, s, heat_sum, npix, T, heatmap, ctx->d_state);
-    LAUNCH_CHECK();
+    RM_TRY(launch_heat_state_init(ctx->d_state, s));
+    RM_TRY(launch_heat_avg_minmax(ctx->d_state, heat_sum, npix, T, heatmap, s));
     if (!xywh) return RM_OK;
     return heatmap_to_roi_impl(ctx, heatmap, H, W, threshold, xywh, nullptr, nullptr, stream, true);
 }
@@ -190,18 +186,8 @@ extern "C" int rm_eulerian_magnification_bandpass(rm_ctx *ctx, const void *frame
         hipLaunchKernelGGL(k_mirror_frames<>, dim3(nblk((size_t)H * W, 256, 1024), (unsigned)(T - Th)), dim3(256), 0, s, raw_buf, T, (size_t)H * W);
         LAUNCH_CHECK();
     }
-    CollapseState *st = ctx->d_state;
-    hipLaunchKernelGGL(k_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, st);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_minmax_plain<>, dim3(nblk(n, 256, 1024)), dim3(256), 0, s, raw_buf, n, st);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_finish_minmax<>, dim3(1), dim3(NSTRIPE), 0, s, st, thr);
-    LAUNCH_CHECK();
-    if (masked) {
-        hipLaunchKernelGGL(k_mask_plain<>, dim3(nblk(n, 256, 8192)), dim3(256), 0, s, raw_buf, n, st, masked);
-        LAUNCH_CHECK();
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->h_state, st, sizeof(CollapseState), hipMemcpyDeviceToHost, s));
+    RM_TRY(threshold_mask(ctx, raw_buf, n, thr, masked, s));
+    HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(CollapseState), hipMemcpyDeviceToHost, s));
     HIP_TRY(stream_wait(s));
     if (minmax_host) { minmax_host[0] = ctx->h_state->min_val; minmax_host[1] = ctx->h_state->max_val; }
     return RM_OK;

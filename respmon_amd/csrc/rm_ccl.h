@@ -26,10 +26,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rm_heat_kernels.h"
+
 namespace rm {
 
 struct CclComp { int root, minx, w1, h1; };   // box: x = minx, y = root / W, width w1 + 1, height h1 + 1
-// (CclBox, the per-root bounding box, is declared next to k_heat_to_u8 in rm_kernels.h)
+// (CclBox, the per-root bounding box, is declared next to k_heat_to_u8 in rm_heat_kernels.h)
 
 __device__ inline bool ccl_bit(const unsigned long long *bits, size_t p) { return (bits[p >> 6] >> (p & 63)) & 1ull; }
 

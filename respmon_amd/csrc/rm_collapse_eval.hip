@@ -1,8 +1,44 @@
 // respmon_amd/csrc/rm_collapse_eval.hip -- collapse, first pass: tile bounds, pruning, exact extrema
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_small_kernels.h"
+#include "rm_select_kernels.h"
+#include "rm_tile_eval.h"
+#include "rm_bounds_l1.h"
 
 using namespace rm;
+
+// The kernels around the reduction state that other units need too, each behind one launcher here.
+int launch_state_init(CollapseState *st, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, st);
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
+int launch_finish_minmax(CollapseState *st, double threshold, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_finish_minmax<>, dim3(1), dim3(NSTRIPE), 0, s, st, threshold);
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
+// transforms.py:184-192 on a materialised [n] array: min, max, top = max - (max - min) * threshold into the state,
+// masked (nullable) = raw with every value >= top replaced by min
+int threshold_mask(rm_ctx *ctx, const double *raw, size_t n, double threshold, double *masked, hipStream_t s)
+{
+    CollapseState *st = ctx->d_state;
+    ctx->state_fresh = false;   // this call reduces into the state
+    RM_TRY(launch_state_init(st, s));
+    hipLaunchKernelGGL(k_minmax_plain<>, dim3(nblk(n, 256, 1024)), dim3(256), 0, s, raw, n, st);
+    LAUNCH_CHECK();
+    RM_TRY(launch_finish_minmax(st, threshold, s));
+    if (masked) {
+        hipLaunchKernelGGL(k_mask_plain<>, dim3(nblk(n, 256, 8192)), dim3(256), 0, s, raw, n, st, masked);
+        LAUNCH_CHECK();
+    }
+    return RM_OK;
+}
 
 // the flat evaluation pass over the listed pairs (exact extrema; values of the kept pairs into the value store)
 int launch_eval_pairs(rm_ctx *ctx, const CollapsePlan &cp, hipStream_t s)
@@ -75,10 +111,7 @@ int collapse_eval(rm_ctx *ctx, const SmallLevels &sl, int T, int t0, int t1, dou
     cp.cS = sl.cS; cp.T = T; cp.t0 = t0; cp.t1 = t1; cp.H = sl.h[0]; cp.W = sl.w[0]; cp.S = sl.S;
     const size_t npix = (size_t)cp.H * cp.W;
     const int Th = sym_frames(T);   // C_S, the bounds and the pairs exist for the unique frames only (rm_kernels.h sym_frame)
-    if (!sl.state_ready) {
-        hipLaunchKernelGGL(k_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, st);
-        LAUNCH_CHECK();
-    }
+    if (!sl.state_ready) RM_TRY(launch_state_init(st, s));
     const int no_prune = (flags & RM_FLAG_NO_PRUNE) ? 1 : 0;
     if (sl.S == 0) {
         if (t0 != 0 || t1 != T) return fail(RM_E_UNSUPPORTED, "frame-sharded calibration needs skip_levels_at_top >= 1");
@@ -103,7 +136,7 @@ int collapse_eval(rm_ctx *ctx, const SmallLevels &sl, int T, int t0, int t1, dou
     RM_TRY(ws(ctx, "pair_list_a", (size_t)npairs, &cp.list_a));
     RM_TRY(ws(ctx, "pair_list_b", (size_t)npairs, &cp.list_b));
     RM_TRY(ws(ctx, "pair_slot", (size_t)npairs, &cp.slot_of));
-    // The value store: 8 KB slots for the pairs the selection keeps, handed out tile by tile (rm_kernels.h k_select_pairs).
+    // The value store: 8 KB slots for the pairs the selection keeps, handed out tile by tile (rm_select_kernels.h k_select_pairs).
     // Capped at STORE_BUDGET_SLOTS (1 GiB): a selection that keeps more takes the dense sum kernel, which needs no store --
     // decided on the device, in this same call (sum_is_dense).  The exhaustive-evaluation baseline (RM_FLAG_NO_PRUNE) and a
     // forced sparse path park every pair they are told to, so they get a slot per pair.

@@ -1,6 +1,9 @@
 // respmon_amd/csrc/rm_collapse_sum.hip -- collapse, second pass: the masked time sum (sparse / dense / store-less forms)
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_select_kernels.h"
+#include "rm_dense_sum.h"
+#include "rm_tile_eval.h"
 
 using namespace rm;
 
@@ -13,16 +16,12 @@ int collapse_sum(rm_ctx *ctx, const CollapsePlan &cp, double thr, double *heat_s
     CollapseState *st = ctx->d_state;
     const size_t npix = (size_t)cp.H * cp.W;
     if (cp.S == 0) {
-        hipLaunchKernelGGL(k_finish_minmax<>, dim3(1), dim3(NSTRIPE), 0, s, st, thr);
-        LAUNCH_CHECK();
+        RM_TRY(launch_finish_minmax(st, thr, s));
         double *sum = heat_sum;
         if (avg_T > 0) RM_TRY(ws(ctx, "heat_sum", npix, &sum));
         hipLaunchKernelGGL(k_masked_sum_plain<>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, cp.cS, cp.T, npix, st, sum);
         LAUNCH_CHECK();
-        if (avg_T > 0) {
-            hipLaunchKernelGGL(k_heat_avg_minmax<>, dim3(nblk(npix, 256, 256)), dim3(256), 0, s, sum, npix, avg_T, heat_sum, st);
-            LAUNCH_CHECK();
-        }
+        if (avg_T > 0) RM_TRY(launch_heat_avg_minmax(st, sum, npix, avg_T, heat_sum, s));
         return RM_OK;
     }
     int *tile_nkept = nullptr;

@@ -353,7 +353,7 @@ int simple_shape_bits_rows(const uint64_t *bits, int H, int W, int y0, int y1, R
     return 1;
 }
 
-// The same rule from the per-row records of k_heat_rows_u8 (rm_kernels.h): rec[y] = first | last << 16 | runs << 32 | 1 << 48 for a row
+// The same rule from the per-row records of k_heat_rows_u8 (rm_heat_kernels.h): rec[y] = first | last << 16 | runs << 32 | 1 << 48 for a row
 // that holds foreground, 0 for one that does not.  *y0 / *y1: first / last row with foreground (y1 < y0: none) -- what the border
 // following needs when the rule does not settle the image.  Returns 1 and fills `out` for ONE hole-free blob, 0 otherwise.
 int simple_shape_row_records(const uint64_t *rec, int H, int W, int *y0, int *y1, RoiResult *out)

@@ -1,6 +1,7 @@
 // respmon_amd/csrc/rm_ctx.hip -- contexts, developer switches, profiling hooks, dtype helpers
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_roi_kernels.h"
 
 using namespace rm;
 

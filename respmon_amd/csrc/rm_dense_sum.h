@@ -2,7 +2,7 @@
 //
 //   heat_sum[y, x] = sum_t (raw[t, y, x] >= top ? min : raw[t, y, x])        transforms.py:184-192 + base.py:562
 //
-// The sparse path (k_select_pairs -> k_eval_pairs -> k_masked_sum_tiles, rm_kernels.h) evaluates the few (tile, frame) pairs
+// The sparse path (k_select_pairs -> k_eval_pairs -> k_masked_sum_tiles, rm_select_kernels.h) evaluates the few (tile, frame) pairs
 // that can hold a value below `top`, parks their values in the value store and sums them afterwards.  When most pairs are
 // such pairs -- skip_levels_at_top = 2 on a noisy video: every 64x16 tile of every frame -- that is one 8 KB round trip
 // through memory per pair on top of single-wave workgroups whose pyrUp steps use a third of their lanes: 12.4 + 5.2 ms at
@@ -14,6 +14,7 @@
 // A pruned pair needs no special case: all of its values are >= top, so every pixel adds `min`, exactly what the sparse
 // path adds for it.
 #pragma once
+#include "rm_kernels.h"
 
 namespace rm {
 

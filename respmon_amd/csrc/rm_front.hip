@@ -1,6 +1,7 @@
 // respmon_amd/csrc/rm_front.hip -- front half of the calibration: frames -> collapsed band-passed level C_S
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_small_kernels.h"
 
 using namespace rm;
 
@@ -36,7 +37,7 @@ void pyr_geom(int H, int W, int levels, int skip, unsigned flags, PyrGeom &pg)
             sg.g_off[l] = 0; sg.np_off[l] = (int)pg.off[l];
             if (l >= S) { sg.g_off[l] = o; o += pg.h[l] * pg.w[l]; }
         }
-        // filter-first form (rm_kernels.h k_small_filter_first): the Gaussian levels and the row-extrema table of the tile
+        // filter-first form (rm_small_kernels.h k_small_filter_first): the Gaussian levels and the row-extrema table of the tile
         // bounds must fit LDS together
         if (!(flags & RM_FLAG_FILTER_LAPLACIANS) && S >= 1 && S < MAX_CHAIN) {
             const size_t nS = (size_t)pg.h[S] * pg.w[S];
@@ -157,10 +158,7 @@ int collapse_levels(rm_ctx *ctx, double *bp, int rows, const PyrGeom &pg, bool s
             RM_TRY(ws(ctx, "tile_lo", (size_t)npairs, &lo));
             RM_TRY(ws(ctx, "tile_hi", (size_t)npairs, &hi));
             RM_TRY(ws(ctx, "sel_cnt", (size_t)cg.tiles_x * cg.tiles_y, &sel_cnt));
-            if (!state_fresh) {   // the lap buffer did not come from front_pyramid on this context just now
-                hipLaunchKernelGGL(k_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, ctx->d_state);
-                LAUNCH_CHECK();
-            }
+            if (!state_fresh) RM_TRY(launch_state_init(ctx->d_state, s));   // the lap buffer did not come from front_pyramid on this context just now
             const size_t sh2 = shmem + tbl;
             if (sh2 > 64 * 1024)
                 HIP_TRY(hipFuncSetAttribute((const void *)k_small_collapse_bounds<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh2));
@@ -241,7 +239,7 @@ int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, doubl
     }
     if (pg.ff_levels) {
         // X_S = B(G_S); X_{L-1} = pyrDown^(L-1-S)(X_S); U_{L-1} = X_{L-1}, U_l = pyrUp(U_{l+1}); C_S = X_S - pyrUp(U_{S+1})
-        // (rm_kernels.h k_small_filter_first: the telescoped collapse, here with one launch per step): only the COARSEST level of
+        // (rm_small_kernels.h k_small_filter_first: the telescoped collapse, here with one launch per step): only the COARSEST level of
         // the filtered pyramid is needed, so the way down is the fused pyrDown chain (rm_down_chain.h) on the float64 level X_S
         RM_TRY(launch_temporal(ctx, lap, T, NP, op, amp, bp, s, ctx->d_state, false, head));   // (its workgroup 0 resets the reduction state: no k_state_init launch)
         out.state_ready = true;
@@ -322,7 +320,7 @@ int make_geom(const SmallLevels &sl, ChainGeom &g)
     g.lds_total = B + (S >= 2 ? std::max(scratch(2), S >= 3 ? small + hb_small : 0) : 0);
     g.tiles_x = (sl.w[0] + CT_W - 1) / CT_W;
     g.tiles_y = (sl.h[0] + CT_H - 1) / CT_H;
-    // weights of the lattice samples (rm_kernels.h lattice_sample): a unit impulse pushed through S interior 1-D pyrUp
+    // weights of the lattice samples (rm_small_kernels.h lattice_sample): a unit impulse pushed through S interior 1-D pyrUp
     // steps (even: (s[j-1] + 6 s[j] + s[j+1]) / 8, odd: (s[j] + s[j+1]) / 2), read at position 1 << S of a 3-pixel line
     {
         double w[3];

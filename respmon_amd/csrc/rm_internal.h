@@ -6,10 +6,10 @@
 //   rm_temporal.hip       temporal filters, materialised min/max mask                   (transforms.py:38-102, 184-192)
 //   rm_down.hip           launchers of the frame-buffer kernels                          (rm_down_chain.h, rm_down_chain_u8.h)
 //   rm_front.hip          frames -> collapsed band-passed level C_S                      (transforms.py:144-182)
-//   rm_collapse_eval.hip  tile bounds, pruning, exact extrema                            (transforms.py:184-186)
+//   rm_collapse_eval.hip  tile bounds, pruning, exact extrema; the reduction state's launchers, threshold_mask   (transforms.py:184-186)
 //   rm_collapse_sum.hip   masked time sum -> heatmap                                     (transforms.py:187-192, base.py:562)
 //   rm_calibrate.hip      rm_calibrate, frame-sharded stages, materialising eulerian_magnification_bandpass
-//   rm_roi.hip            heatmap -> ROI, sparse heatmap packets                         (base.py:563-575)
+//   rm_roi.hip            heatmap -> ROI, sparse heatmap packets; the heatmap extrema's launchers   (base.py:563-575)
 //   rm_locate.hip         rm_locate, rm_locate_submit / rm_locate_result                 (base.py:547-601)
 //   rm_comm.hip           RCCL behind the C-ABI                                          
 //   rm_motion.hip         ROI mean / crop, corners, LK, PCA; the ROI means and the LK flow of several subjects (base.py:354-407; rm_subjects.h, rm_flow_multi.h)
@@ -17,8 +17,13 @@
 //   rm_magnify.hip        rm_magnify, rm_magnify_bgr: frames + band-passed motion in one pass            (transforms.py:170, 181; rm_magnify.h)
 //   rm_stream.hip         rm_sosfilt, rm_stream_*: the causal band-pass in second-order sections with carried state, a live stream magnified chunk by chunk (rm_stream_kernels.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
-// Every kernel header is included by every unit; non-template kernels are `static`, so a unit generates code only for the kernels
-// it launches.
+// A kernel is compiled in the ONE unit that launches it.  This header therefore includes no kernel header beyond what its own
+// declarations need (rm_kernels.h: the geometry structs, CollapseState, SumPlan; rm_flow_ws.h: rm_ctx embeds a FlowWorkspace) and what
+// the frame-buffer units expect from it (rm_down_chain.h, rm_down_chain_u8.h: templates, compiled where they are launched); every
+// .hip includes the stage headers whose kernels it launches (the table in rm_kernels.h).  A kernel several units need is reached
+// through one small host launcher in one of them, declared below (launch_pyr_up, launch_state_init, threshold_mask, ...), and a
+// host function that launches a kernel is never defined in a header several units include: an inline launcher would instantiate
+// its kernels in every one of them.  tools/check_resources.py fails the build when a kernel is compiled twice.
 #pragma once
 #include "../../include/respmon_hip.h"
 #include "../../include/respmon_hip_debug.h"
@@ -41,12 +46,8 @@
 #include "rm_kernels.h"
 #include "rm_down_chain.h"
 #include "rm_down_chain_u8.h"
-#include "rm_dense_sum.h"
-#include "rm_tile_eval.h"
-#include "rm_bounds_l1.h"
-#include "rm_ccl.h"
-#include "rm_flow.h"
-#include "rm_subjects.h"
+#include "rm_flow_ws.h"
+namespace rm { struct CclComp; }   // rm_ccl.h (rm_roi.hip)
 
 // sets the thread's error string (rm_last_error_string) and returns `code`
 int fail(int code, const char *fmt, ...);
@@ -339,6 +340,9 @@ int front_half(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int W, 
 int make_geom(const SmallLevels &sl, rm::ChainGeom &g);
 
 // ---- rm_collapse_eval.hip / rm_collapse_sum.hip
+int launch_state_init(rm::CollapseState *st, hipStream_t s);                          // k_state_init
+int launch_finish_minmax(rm::CollapseState *st, double threshold, hipStream_t s);     // k_finish_minmax: min, max, top from what was reduced
+int threshold_mask(rm_ctx *ctx, const double *raw, size_t n, double threshold, double *masked, hipStream_t s);   // the four steps of transforms.py:184-192 on a materialised array
 int launch_eval_pairs(rm_ctx *ctx, const CollapsePlan &cp, hipStream_t s);
 int collapse_eval(rm_ctx *ctx, const SmallLevels &sl, int T, int t0, int t1, double thr, unsigned flags, CollapsePlan &cp, hipStream_t s);
 int collapse_sum(rm_ctx *ctx, const CollapsePlan &cp, double thr, double *heat_sum, hipStream_t s, int avg_T = 0, bool host_rescue = false);
@@ -351,6 +355,10 @@ int calibrate_impl(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int
 // ---- rm_magnify.hip: the sum kernels with a row of C_S per frame (rm_stream.hip)
 int magnify_rows(rm_ctx *ctx, const void *frames, int dtype, int n, int H, int W, const SmallLevels &sl, void *out, int out_dtype, hipStream_t s);
 
+// ---- rm_roi.hip: the heatmap extrema in the state (k_heat_state_init; + k_heat_minmax; k_heat_avg_minmax)
+int launch_heat_state_init(rm::CollapseState *st, hipStream_t s);
+int launch_heat_minmax(rm::CollapseState *st, const double *heat, size_t npix, hipStream_t s);
+int launch_heat_avg_minmax(rm::CollapseState *st, const double *heat_sum, size_t npix, int T, double *heat, hipStream_t s);
 // ---- rm_roi.hip: the ROI stage in two halves (device launches, then -- once they have been waited for -- the host contour stage)
 int roi_launch(rm_ctx *ctx, const double *heat, int H, int W, int threshold, uint8_t *avg_u8, uint8_t *binary, void *stream, bool have_minmax,
                RoiPending &pd, bool xywh_given);

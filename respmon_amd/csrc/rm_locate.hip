@@ -43,8 +43,7 @@ extern "C" int rm_locate(rm_ctx *ctx, const void *frames, int dtype, int T, int 
         // is what looking at the flag first would take): take the sum with the dense kernel, now that the stream is idle, and
         // extract the ROI again
         hipStream_t s = (hipStream_t)stream;
-        hipLaunchKernelGGL(k_heat_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, ctx->d_state);
-        LAUNCH_CHECK();
+        RM_TRY(launch_heat_state_init(ctx->d_state, s));
         // how many pairs did the selection keep?  A store that holds them (up to STORE_MAX_SLOTS) is allocated -- for this call and the
         // later ones of the context -- and the evaluation + sum run again through it; beyond that the store-less sum takes over
         HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(CollapseState), hipMemcpyDeviceToHost, s));

@@ -36,6 +36,8 @@
 //   - where nothing is filtered (skip >= levels - 1) raw is zero and a byte k becomes u8(k * (1./255)): the reference's
 //     float_to_uint8(uint8_to_float(k)), which is k - 1 on 24 of the 256 levels.  NOT an identity copy: the rule of the gray path, kept.
 #pragma once
+#include "rm_down_chain_u8.h"   // bgr8_t
+#include "rm_tile_eval.h"
 
 namespace rm {
 

@@ -1,6 +1,8 @@
 // respmon_amd/csrc/rm_motion.hip -- ROI reductions and motion extraction (base.py:354-407), for one subject and for several
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_roi_kernels.h"
+#include "rm_subjects.h"
 #include "rm_flow_multi.h"
 
 using namespace rm;

@@ -1,6 +1,7 @@
 // respmon_amd/csrc/rm_pyramid.hip -- pyramid building blocks and the materialising pyramid API (pyramid.py:9-69)
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_pyr_kernels.h"
 
 using namespace rm;
 
@@ -12,13 +13,11 @@ int launch_pyr_down(const void *src, int dtype, int T, int h, int w, double *dst
     int dh = (h + 1) / 2, dw = (w + 1) / 2;
     dim3 grid((dw + PD_TX - 1) / PD_TX, (dh + PD_TY - 1) / PD_TY, T), block(256);
     size_t fs = (size_t)h * w;
-    switch (dtype) {
-    case RM_U8: hipLaunchKernelGGL((k_pyr_down<uint8_t>), grid, block, 0, s, (const uint8_t *)src, h, w, fs, dst, dh, dw); break;
-    case RM_F16: hipLaunchKernelGGL((k_pyr_down<__half>), grid, block, 0, s, (const __half *)src, h, w, fs, dst, dh, dw); break;
-    case RM_F32: hipLaunchKernelGGL((k_pyr_down<float>), grid, block, 0, s, (const float *)src, h, w, fs, dst, dh, dw); break;
-    case RM_F64: hipLaunchKernelGGL((k_pyr_down<double>), grid, block, 0, s, (const double *)src, h, w, fs, dst, dh, dw); break;
-    default: return fail(RM_E_BADARG, "unknown dtype %d", dtype);
-    }
+    if (!valid_dtype(dtype)) return fail(RM_E_BADARG, "unknown dtype %d", dtype);
+    dispatch_dtype(dtype, [&](auto t) {
+        using Tin = decltype(t);
+        hipLaunchKernelGGL((k_pyr_down<Tin>), grid, block, 0, s, (const Tin *)src, h, w, fs, dst, dh, dw);
+    });
     LAUNCH_CHECK();
     return RM_OK;
 }
@@ -69,13 +68,11 @@ __global__ __launch_bounds__(256) void k_to_f64(const Tin *src, double *dst, siz
 int launch_to_f64(const void *src, int dtype, size_t n, double *dst, hipStream_t s)
 {
     dim3 grid(nblk(n, 256)), block(256);
-    switch (dtype) {
-    case RM_U8: hipLaunchKernelGGL((k_to_f64<uint8_t>), grid, block, 0, s, (const uint8_t *)src, dst, n); break;
-    case RM_F16: hipLaunchKernelGGL((k_to_f64<__half>), grid, block, 0, s, (const __half *)src, dst, n); break;
-    case RM_F32: hipLaunchKernelGGL((k_to_f64<float>), grid, block, 0, s, (const float *)src, dst, n); break;
-    case RM_F64: hipLaunchKernelGGL((k_to_f64<double>), grid, block, 0, s, (const double *)src, dst, n); break;
-    default: return fail(RM_E_BADARG, "unknown dtype %d", dtype);
-    }
+    if (!valid_dtype(dtype)) return fail(RM_E_BADARG, "unknown dtype %d", dtype);
+    dispatch_dtype(dtype, [&](auto t) {
+        using Tin = decltype(t);
+        hipLaunchKernelGGL((k_to_f64<Tin>), grid, block, 0, s, (const Tin *)src, dst, n);
+    });
     LAUNCH_CHECK();
     return RM_OK;
 }

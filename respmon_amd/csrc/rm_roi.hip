@@ -1,6 +1,8 @@
 // respmon_amd/csrc/rm_roi.hip -- heatmap -> ROI (base.py:563-575) and the sparse heatmap packets
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_heat_kernels.h"
+#include "rm_ccl.h"
 
 using namespace rm;
 
@@ -9,6 +11,31 @@ constexpr int LABEL_REPROBE = 64;         // labelled stages in a row before the
 constexpr int LABEL_MIN_CONTOURS = 512;   // ~0.13 us per followed border on the host against ~40 us of labelling kernels
 constexpr long long LABEL_MIN_STEPS = 24000;   // ... or this many border steps (5-10 ns each, cache misses included) against ~100 us of labelling kernels
 static_assert(sizeof(CclComp) == sizeof(LabelComp), "record layout shared by rm_ccl.h and rm_contour.h");
+
+// The heatmap extrema in the reduction state: reset, the min / max of an existing heatmap, the average of a time sum with its
+// min / max.  Other units reach these kernels through the launchers here.
+int launch_heat_state_init(CollapseState *st, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_heat_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, st);
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
+int launch_heat_minmax(CollapseState *st, const double *heat, size_t npix, hipStream_t s)
+{
+    RM_TRY(launch_heat_state_init(st, s));
+    hipLaunchKernelGGL(k_heat_minmax<>, dim3(nblk(npix, 256, 256)), dim3(256), 0, s, heat, npix, st);
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
+// heat = heat_sum / T; the caller (or a sum kernel in front) has reset the heatmap extrema
+int launch_heat_avg_minmax(CollapseState *st, const double *heat_sum, size_t npix, int T, double *heat, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_heat_avg_minmax<>, dim3(nblk(npix, 256, 256)), dim3(256), 0, s, heat_sum, npix, T, heat, st);
+    LAUNCH_CHECK();
+    return RM_OK;
+}
 
 // The ROI stage in two halves: roi_launch enqueues the device work (threshold -> packed image in the pinned memory of slot
 // ctx->cur_slot, component labelling when the rule asks for it), roi_finish -- once the stream (or the event recorded behind the
@@ -57,12 +84,7 @@ int roi_launch(rm_ctx *ctx, const double *heat, int H, int W, int threshold, uin
     HIP_TRY(hipHostGetDevicePointer((void **)&dev_bin, rs.h_bin, 0));
     PhaseTimer *pt_roi = new PhaseTimer(ctx, 3, s);
     struct Guard { PhaseTimer *&p; ~Guard() { delete p; p = nullptr; } } guard{pt_roi};
-    if (!have_minmax) {  // rm_calibrate has just left the heatmap's min / max in the state
-        hipLaunchKernelGGL(k_heat_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, st);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_heat_minmax<>, dim3(nblk(npix, 256, 256)), dim3(256), 0, s, heat, npix, st);
-        LAUNCH_CHECK();
-    }
+    if (!have_minmax) RM_TRY(launch_heat_minmax(st, heat, npix, s));  // (otherwise rm_calibrate has just left the heatmap's min / max in the state)
     // noisy images: label the components on the device so that the host follows only borders that can win (rm_ccl.h)
     const bool clip = ctx->clip_frame || clip_once;
     const bool same_geom = ctx->label_H == H && ctx->label_W == W;
@@ -289,10 +311,7 @@ int heatmap_to_rois_impl(rm_ctx *ctx, const double *heat, int H, int W, int thre
     RM_TRY(ws(ctx, "subjects_bits", nwords, &d_bits));
     CollapseState *st = ctx->d_state;
     ctx->state_fresh = false;   // the heatmap extrema are reduced into the state
-    hipLaunchKernelGGL(k_heat_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, st);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_heat_minmax<>, dim3(nblk(npix, 256, 256)), dim3(256), 0, s, heat, npix, st);
-    LAUNCH_CHECK();
+    RM_TRY(launch_heat_minmax(st, heat, npix, s));
     hipLaunchKernelGGL(k_heat_to_u8<>, dim3(nblk(npix, 256, 2048)), dim3(256), 0, s, heat, npix, W, st, threshold, (uint8_t *)nullptr, (uint8_t *)nullptr,
                        (unsigned long long *)nullptr, (uint8_t *)nullptr, d_bits, (int *)nullptr, (CclBox *)nullptr, (unsigned int *)nullptr,
                        (const int *)nullptr);

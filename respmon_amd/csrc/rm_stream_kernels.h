@@ -29,6 +29,7 @@
 //              steady state of a constant input x[0].  A band-pass has no DC gain, so the stream does not begin with seconds of ringing
 //              from the step 0 -> first frame.
 #pragma once
+#include "rm_kernels.h"
 
 namespace rm {
 

@@ -2,7 +2,7 @@
 // (rm_roi_mean_multi_clip).  The ranked contour list the rectangles usually come from (rm_heatmap_to_rois / rm_locate_multi) is a
 // host stage: rm_contour.cpp ranked_external_contours_bits.
 #pragma once
-#include "rm_kernels.h"
+#include "rm_roi_kernels.h"
 
 namespace rm {
 

@@ -1,6 +1,8 @@
 // respmon_amd/csrc/rm_temporal.hip -- temporal filters (transforms.py:38-102) and the materialised min/max mask (transforms.py:184-192)
 // (one translation unit of librespmon_hip.so; shared host-side declarations: rm_internal.h)
 #include "rm_internal.h"
+#include "rm_temporal_kernels.h"
+#include "rm_roi_kernels.h"
 
 using namespace rm;
 
@@ -223,7 +225,7 @@ static int launch_temporal_forms(rm_ctx *ctx, const double *x, int T, size_t NP,
     const int Th = sym_frames(T);
     if (op.nk == 0) {  // nothing survives the mask
         HIP_TRY(hipMemsetAsync(out, 0, sizeof(double) * (size_t)(full ? T : Th) * NP, s));
-        if (st_init) { hipLaunchKernelGGL(k_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, st_init); LAUNCH_CHECK(); }
+        if (st_init) RM_TRY(launch_state_init(st_init, s));
         return RM_OK;
     }
     const int mirror_n = full ? T : 0;
@@ -285,12 +287,10 @@ extern "C" int rm_time_average(rm_ctx *ctx, const void *data, int dtype, int T, 
     if (npix == 0) return RM_OK;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)((npix + 255) / 256)), block(256);
-    switch (dtype) {
-    case RM_U8: hipLaunchKernelGGL((k_time_average<uint8_t>), grid, block, 0, s, (const uint8_t *)data, T, npix, out); break;
-    case RM_F16: hipLaunchKernelGGL((k_time_average<__half>), grid, block, 0, s, (const __half *)data, T, npix, out); break;
-    case RM_F32: hipLaunchKernelGGL((k_time_average<float>), grid, block, 0, s, (const float *)data, T, npix, out); break;
-    default: hipLaunchKernelGGL((k_time_average<double>), grid, block, 0, s, (const double *)data, T, npix, out); break;
-    }
+    dispatch_dtype(dtype, [&](auto t) {
+        using Tin = decltype(t);
+        hipLaunchKernelGGL((k_time_average<Tin>), grid, block, 0, s, (const Tin *)data, T, npix, out);
+    });
     LAUNCH_CHECK();
     return RM_OK;
 }
@@ -314,28 +314,16 @@ extern "C" int rm_lfilter(rm_ctx *ctx, const double *data, int T, size_t npix, c
     return RM_OK;
 }
 
-// transforms.py:184-192 on a materialised [n] array: min, max, top = max - (max - min) * threshold,
-// masked = raw with every value >= top replaced by min
+// transforms.py:184-192 on a materialised [n] array (threshold_mask, rm_collapse_eval.hip)
 extern "C" int rm_threshold_mask(rm_ctx *ctx, const double *raw, size_t n, double threshold, double *masked, double *minmax_host,
                                  void *stream)
 {
     if (!ctx || !raw || n == 0) return fail(RM_E_BADARG, "rm_threshold_mask: bad argument");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ctx->device));
-    CollapseState *st = ctx->d_state;
-    hipLaunchKernelGGL(k_state_init<>, dim3(1), dim3(NSTRIPE), 0, s, st);
-    ctx->state_fresh = false;   // this call reduces into the state
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_minmax_plain<>, dim3(nblk(n, 256, 1024)), dim3(256), 0, s, raw, n, st);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_finish_minmax<>, dim3(1), dim3(NSTRIPE), 0, s, st, threshold);
-    LAUNCH_CHECK();
-    if (masked) {
-        hipLaunchKernelGGL(k_mask_plain<>, dim3(nblk(n, 256, 8192)), dim3(256), 0, s, raw, n, st, masked);
-        LAUNCH_CHECK();
-    }
+    RM_TRY(threshold_mask(ctx, raw, n, threshold, masked, s));
     if (minmax_host) {
-        HIP_TRY(hipMemcpyAsync(ctx->h_state, st, sizeof(CollapseState), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(CollapseState), hipMemcpyDeviceToHost, s));
         HIP_TRY(stream_wait(s));
         minmax_host[0] = ctx->h_state->min_val;
         minmax_host[1] = ctx->h_state->max_val;

@@ -3,7 +3,7 @@
 //   raw[t] = pyrUp^S(C_S[t])                        (pyramid.py:51-57 below `skip`: transforms.py:150-160 leaves those levels zero)
 //   heat   = (1 / T) sum_t (raw[t] >= top ? min : raw[t])      (transforms.py:184-192, base.py:562), sequentially in t
 //
-// The generic evaluation of a kept (tile, frame) pair (rm_kernels.h k_eval_pairs: a single-wave workgroup runs the pyrUp chain in LDS)
+// The generic evaluation of a kept (tile, frame) pair (rm_select_kernels.h k_eval_pairs: a single-wave workgroup runs the pyrUp chain in LDS)
 // costs ~2 800 instructions per pair and 20+ us of latency; with the value store behind it (8 KB per pair) and k_masked_sum_tiles that
 // was 28 + 21 us per step at 1080p x 256 for 2 600 pairs, 21 MB written and read back.  Here:
 //   * TileEval<S> (TileFoot / TileSetup / tile_setup / te_step / tile_eval / tile_eval_below): ONE wave evaluates a 64 x 16 tile of
@@ -24,6 +24,7 @@
 //     written.
 // rm_magnify.h (k_magnify) and rm_bounds_l1.h (k_bounds_up1) use TileEval too.
 #pragma once
+#include "rm_dense_sum.h"
 
 namespace rm {
 
@@ -255,7 +256,7 @@ __global__ __launch_bounds__(64) void k_eval_c(const double *cS, ChainGeom g, in
     }
 }
 
-// ---- the flat evaluation pass of the sparse path with the wave-private evaluator (k_eval_pairs' job, rm_kernels.h) ---------------------
+// ---- the flat evaluation pass of the sparse path with the wave-private evaluator (k_eval_pairs' job, rm_select_kernels.h) ---------------------
 // One wave per listed pair, every SIMD of the chip busy whatever tile the pairs belong to: exact min / max from all evaluated pairs,
 // the values of the kept ones parked in their slot of the value store ([slot][row][column], 16 bytes per lane and row) for
 // k_masked_sum_tiles.  ~500 instructions per pair instead of ~2 800.

@@ -9,7 +9,7 @@ using namespace rm;
 // The ring holds what front_pyramid writes for a frame (G_S, or the Laplacian levels S .. L-2: PyrGeom::NP doubles), float64 whatever
 // the frames were.  Frame j of the stream (counted from the last reset) sits in row j mod T, so with `count` frames held the oldest
 // one is row `head` (0 until the ring is full) and the next one goes to row (head + count) mod T.  The temporal kernels read the
-// chronological window in place (rm_kernels.h ring_row); nothing behind them knows about the ring.
+// chronological window in place (rm_temporal_kernels.h ring_row); nothing behind them knows about the ring.
 struct rm_window {
     int device = 0;
     int T = 0, H = 0, W = 0, levels = 0, skip = 0;

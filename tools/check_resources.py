@@ -1,6 +1,9 @@
 """Parse hipcc's -Rpass-analysis=kernel-resource-usage remarks (respmon_amd/csrc/build_resources.txt, written by the Makefile) into a
 table and FAIL when a frame-buffer kernel of the shipped library uses scratch (spilled registers): those kernels stream the
 [T,H,W] buffer and every spilled VGPR is HBM traffic on top of it (1.60x the algorithmic bytes on the uint8 chain).
+FAIL as well when a kernel occurs more than once in the report: every kernel is compiled in the one translation unit that launches it
+(respmon_amd/csrc/rm_internal.h).  A second copy means that a header several units include has begun to launch it, or that two units
+launch it themselves instead of going through one launcher.
 
     python tools/check_resources.py [remarks file] [--all]      exit code 1 on a violation
 """
@@ -19,6 +22,9 @@ DEFAULT = os.path.join(ROOT, "respmon_amd", "csrc", "build_resources.txt")
 MUST_NOT_SPILL = re.compile(r"^(void )?rm::k_down_chain<[^>]*, false>|^(void )?rm::k_down_chain_u8<|^(void )?rm::k_down_chain_narrow<|"
                             r"^(void )?rm::k_magnify<|^(void )?rm::k_roi_mean_multi_clip<|"
                             r"^(void )?rm::k_lk_track_multi_clip<|^(void )?rm::k_sosfilt<")
+# kernels (mangled names, as the report spells them) that may be compiled in more than one unit, each with its reason.  None: wherever
+# several units need a kernel, one of them holds a launcher for it (launch_state_init, threshold_mask, launch_heat_minmax, ...).
+MAY_REPEAT = set()
 
 
 def demangle(names):
@@ -66,10 +72,19 @@ def main():
         if show_all or must or scratch > 0:
             print("%-72s %5s %5s %8d %6s %4s%s" % (r["demangled"][:72], r.get("VGPRs", "?"), r.get("AGPRs", "?"), scratch, r.get("VGPRs Spill", "?"),
                                                  r.get("Occupancy [waves/SIMD]", "?"), "   <-- must not spill" if must and scratch else ""))
+    copies = {}
+    for r in rows:
+        copies[r["name"]] = copies.get(r["name"], 0) + 1
+    repeated = sorted(n for n, c in copies.items() if c > 1 and n not in MAY_REPEAT)
+    for n, d in zip(repeated, demangle(repeated)):
+        print("%-72s compiled in %d units" % (d.split("(")[0][:72], copies[n]))
     if bad:
         print("check_resources: %d frame-buffer kernel(s) use scratch" % len(bad))
+    if repeated:
+        print("check_resources: %d kernel(s) are compiled in more than one translation unit" % len(repeated))
+    if bad or repeated:
         return 1
-    print("check_resources: ok (%d kernels, frame-buffer kernels hold their state in registers)" % len(rows))
+    print("check_resources: ok (%d kernels, each compiled once, frame-buffer kernels hold their state in registers)" % len(rows))
     return 0
 
 
