@@ -398,8 +398,8 @@ int rm_roi_to_uint8(rm_ctx *ctx, const void *frame_dev, int dtype, int H, int W,
                     uint8_t *dst_dev, void *stream);
 
 /* ---- base.py:365-366 cv2.goodFeaturesToTrack(img_u8, mask=None, maxCorners, qualityLevel,
- *      minDistance, blockSize).  pts_host: float32 (x,y) pairs, capacity max_corners; *n_host = count
- *      (0 <=> cv2 returns None; always 0 when h < 3 or w < 3). */
+ *      minDistance, blockSize).  pts_host: float32 (x,y) pairs, capacity max_corners, or h * w when max_corners <= 0 (no
+ *      limit, as in OpenCV); *n_host = count (0 <=> cv2 returns None; always 0 when h < 3 or w < 3). */
 int rm_good_features_to_track(rm_ctx *ctx, const uint8_t *img_dev, int h, int w, int max_corners,
                               double quality_level, double min_distance, int block_size,
                               float *pts_host, int *n_host, void *stream);
@@ -423,7 +423,8 @@ int rm_pca_reduce(rm_ctx *ctx, const float *motion_host, int n, double *out_host
 /* ---- base.py:363-388 as ONE call per frame (SURVEY 8b "rm_flow_step"): the ROI crop, its pyramids, the tracked points and
  *      their status never leave the device between two frames.
  *      rm_flow_begin = base.py:364-366: crop + float_to_uint8 of the ROI, cv2.goodFeaturesToTrack on it; the corners are
- *        returned (pts_host, capacity max(max_corners, 1) float32 pairs; *n_host = 0 <=> cv2 returns None) and kept on the device.
+ *        returned (pts_host, capacity max_corners float32 pairs, or w * h when max_corners <= 0: no limit; *n_host = 0 <=> cv2
+ *        returns None) and kept on the device.
  *      rm_flow_step  = base.py:371-388: crop of the new frame, cv2.calcOpticalFlowPyrLK from the previous crop and the kept
  *        points, np.mean(good_old - good_new, axis=0) over status == 1 (float32, point order) -> mean_xy_host[2], *n_good_host;
  *        the new crop and p1[st == 1] become the state the next call starts from (base.py:381-382).  With no points left the

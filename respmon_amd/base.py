@@ -191,7 +191,7 @@ class _Backend:
     def good_features_to_track(self, img_u8, maxCorners, qualityLevel, minDistance, blockSize):
         import ctypes
         h, w = img_u8.shape
-        cap = max(int(maxCorners), 1)
+        cap = int(maxCorners) if maxCorners > 0 else h * w        # (maxCorners <= 0: no limit)
         pts = np.empty((cap, 2), dtype=np.float32)
         n = ctypes.c_int()
         _capi.check(self.lib, self.lib.rm_good_features_to_track(device.ctx(), device.ptr(img_u8), h, w, int(maxCorners),
@@ -242,7 +242,7 @@ class _Backend:
     def flow_begin(self, state, gray_u8, x, y, w, h, maxCorners, qualityLevel, minDistance, blockSize):
         import ctypes
         H, W = gray_u8.shape
-        pts = np.empty((max(int(maxCorners), 1), 2), dtype=np.float32)
+        pts = np.empty((int(maxCorners) if maxCorners > 0 else w * h, 2), dtype=np.float32)        # (maxCorners <= 0: no limit)
         n = ctypes.c_int()
         _capi.check(self.lib, self.lib.rm_flow_begin(device.ctx(), state.handle, device.ptr(gray_u8), device.dtype_code(gray_u8), H, W, x, y, w, h,
                                                      int(maxCorners), float(qualityLevel), float(minDistance), int(blockSize),

@@ -154,7 +154,8 @@ extern "C" int rm_flow_begin(rm_ctx *ctx, rm_flow_state *state, const void *fram
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ctx->device));
     FlowState &fs = state->fs;
-    fs.w = w; fs.h = h; fs.cap = std::max(max_corners, 1); fs.flip = 0; fs.npts = 0; fs.begun = false;
+    // (max_corners <= 0: no limit, as in OpenCV -- at most one corner per pixel)
+    fs.w = w; fs.h = h; fs.cap = max_corners > 0 ? max_corners : w * h; fs.flip = 0; fs.npts = 0; fs.begun = false;
     fs.pyr_levels[0] = fs.pyr_levels[1] = -1; fs.deriv_levels[0] = fs.deriv_levels[1] = -1;
     if (!fs.res) HIP_TRY(hipHostMalloc((void **)&fs.res, 4 * sizeof(float), hipHostMallocDefault));
     uint8_t *crop = nullptr; float *pa = nullptr, *pb = nullptr;

@@ -304,7 +304,7 @@ def _flow_methods():
     def flow_begin(self, frame_u8, x, y, w, h, maxCorners=100, qualityLevel=0.3, minDistance=7, blockSize=7, state=None):
         f = np.ascontiguousarray(frame_u8, dtype=np.uint8)
         H, W = f.shape
-        pts = np.empty((max(int(maxCorners), 1), 2), np.float32)
+        pts = np.empty((int(maxCorners) if maxCorners > 0 else w * h, 2), np.float32)
         n = ctypes.c_int()
         if getattr(self, "_fstate", None) is None:
             self._fstate = self.flow_state()

@@ -172,7 +172,8 @@ def reference_crop(oracle, frame_u8):
 
 
 def sweep_corners(be, oracle, texture):
-    """Every small crop, textured and flat, blockSize 3 and 5: be.gftt(img, blockSize) and be.begin(img, blockSize) (the resident
+    """Every small crop, textured and flat, blockSize 3, 5 and 7 (7 is the reference's; on crops 3 to 6 pixels wide its reflect-101
+    border wraps more than once): be.gftt(img, blockSize) and be.begin(img, blockSize) (the resident
     path, whole frame = the crop, so its image is reference_crop(img)) must return None exactly when the oracle does, and the same
     corners otherwise."""
     ncases = 0
@@ -180,7 +181,7 @@ def sweep_corners(be, oracle, texture):
         for w in SMALL:
             a, _, flat = crop_pair(texture, h, w)
             for img in (a, flat):
-                for bs in (3, 5):
+                for bs in (3, 5, 7):
                     for got, src in ((be.gftt(img, bs), img), (be.begin(img, bs), reference_crop(oracle, img))):
                         ref = oracle.goodFeaturesToTrack(src, FEATURE["maxCorners"], FEATURE["qualityLevel"], FEATURE["minDistance"],
                                                          blockSize=bs)

@@ -43,7 +43,7 @@ class _EmuAdapter:
 
 def test_emu_corners_on_every_small_crop(emu, oracle):
     n = mr.sweep_corners(_EmuAdapter(emu), oracle, synth.synth_texture(64, 64, seed=23))
-    assert n == len(mr.SMALL) ** 2 * 2 * 2 * 2
+    assert n == len(mr.SMALL) ** 2 * 2 * 3 * 2
 
 
 def test_emu_narrow_crops_have_no_corners(emu):

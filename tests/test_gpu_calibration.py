@@ -901,6 +901,7 @@ def test_contour_stage_device_labelling(hip, oracle):
     import torch
     import scipy.ndimage as ndi
     from respmon_amd import dist
+    from tests import roi_reference
     rng = np.random.default_rng(2024)
     cases = []
     for (h, w, dens) in [(720, 1280, 0.16), (720, 1280, 0.45), (1080, 1920, 0.30), (2160, 3840, 0.02), (2160, 3840, 0.62),
@@ -964,6 +965,7 @@ def test_contour_stage_device_labelling(hip, oracle):
         assert n_l == ndi.label(m, structure=np.ones((3, 3)))[1], m.shape
         if m.size <= 1300 * 800:
             assert roi_l == oracle.roi_from_heatmap_u8(np.where(m, 255, 0).astype(np.uint8), 20), m.shape
+        assert roi_l == roi_reference.winner(m), m.shape     # every size, the 4K ones included: block counts, no border followed
     assert fired >= 1
     # more components than the record list holds (2^18): the host follows every border of the image it has anyway
     m = rng.random((2160, 3840)) < 0.16
@@ -979,6 +981,7 @@ def test_contour_stage_device_labelling(hip, oracle):
     want = {}
     for name, img in (("blob", blob4k), ("two", two4k), ("overflow", m)):
         want[name] = dist.hip_heatmap_to_roi(torch.from_numpy(img.astype(np.float64)).cuda(), 20, labelling=False)
+        assert want[name] == roi_reference.winner(img), name
     for lazy in (1, 0):
         device.debug_set("label_lazy", lazy)
         try:

@@ -126,12 +126,12 @@ def test_extract_motion_flow_state_machine(oracle):
 def test_flow_against_float64_brute_force_and_component_boxes(be, oracle):
     """Cross-checks of the PRODUCT that involve neither cv2 nor the oracle's restatement of it (VERDICT r1 Next 6b):
     (i) rm_calc_optical_flow_pyr_lk against a plain float64 Lucas-Kanade on the config-3 texture, within 1e-2 px;
-    (ii) rm_heatmap_to_roi against scipy.ndimage's connected components: the ROI is the bounding box of one 8-connected
-    component of the thresholded heatmap, and no other component has a larger box area than ... the polygon-area winner's
-    component is among the components (sanity: the box of the largest-pixel-count component when blobs are convex)."""
+    (ii) rm_heatmap_to_roi against tests/roi_reference.py: the ROI is the box of the external component with the largest contour
+    area (block counts on scipy.ndimage's hole-filled components), ties to the last in raster order."""
     import torch
     import scipy.ndimage as ndi
     from tests import lk_bruteforce as bf
+    from tests import roi_reference
     from respmon_amd import dist
     a, b, pts, (dx, dy) = bf.config3_case(oracle)
     p1, st = be.calc_optical_flow_pyr_lk(_dev(a), _dev(b), pts.reshape(-1, 1, 2), winSize=(15, 15), maxLevel=2, criteria=(3, 10, 0.03))
@@ -148,16 +148,8 @@ def test_flow_against_float64_brute_force_and_component_boxes(be, oracle):
         thr = int(rng.integers(120, 200))
         roi = dist.hip_heatmap_to_roi(torch.from_numpy(heat).cuda(), thr)
         u8 = (np.floor((heat - heat.min()) / (heat.max() - heat.min()) * 255)).astype(np.int64)   # truncating float_to_uint8, no oracle
-        lab, n = ndi.label(u8 > thr, structure=np.ones((3, 3)))
-        boxes = [(sl[1].start, sl[0].start, sl[1].stop - sl[1].start, sl[0].stop - sl[0].start) for sl in ndi.find_objects(lab)]
-        if n == 0:
-            assert roi is None
-            continue
-        assert roi in boxes                                  # a true component's bounding box, found without border following
-        # smooth blobs: the component with the largest polygon area is, up to ties among near-equal blobs, the one whose filled
-        # region is largest -- its box must not be smaller than HALF the largest component's (a gross mis-selection would be)
-        sizes = ndi.sum(np.ones_like(lab), lab, index=np.arange(1, n + 1))
-        assert sizes[boxes.index(roi)] >= 0.5 * sizes.max()
+        # the contour-area winner by block counts on the hole-filled components, found without border following (None: no component)
+        assert roi == roi_reference.winner(u8 > thr), (k, roi)
 
 
 def test_flow_step_resident_equals_four_calls(oracle):

@@ -66,10 +66,10 @@ def _smooth_noise(H, W, seed, sigma=2.0):
 
 
 def test_corners_on_every_small_crop(be, oracle):
-    """(a) h, w in {1..23}^2, textured and flat, blockSize 3 and 5, both entry points: None exactly when the oracle says so."""
+    """(a) h, w in {1..23}^2, textured and flat, blockSize 3, 5 and 7, both entry points: None exactly when the oracle says so."""
     n = mr.sweep_corners(_GpuAdapter(be), oracle, synth.synth_texture(64, 64, seed=23))
     print("motion-edges: %d corner cases" % n)
-    assert n == len(mr.SMALL) ** 2 * 2 * 2 * 2
+    assert n == len(mr.SMALL) ** 2 * 2 * 3 * 2
 
 
 def test_lk_on_every_small_crop(be, oracle):
