@@ -41,6 +41,22 @@ int rm_debug_counters(rm_ctx *ctx, long long *out_host, void *stream);
  * stamp of the library they were measured on; bench.py reports them only while the stamps agree. */
 const char *rm_debug_kernel_source_stamp(void);
 
+/* The frame-buffer kernel's hand-off of its segment boundary (float64 buffers, two segments per frame; DESIGN 4.1 "the stitch";
+ * switches "dc_stitch" 0|1, "dc_stitch_count" 0|1, test hooks "dc_stitch_swap" 0|1 and "dc_stitch_stall_frame" f (-1: none)).
+ * Fills out_host[0 .. RM_CHAIN_STITCH_WORDS) for the launch a float64 [T,H,W] buffer with 16-byte aligned rows and a chain of depth
+ * S would get under the context's switches ("dc_segs", "dc_wpg", "dc_split", "dc_stitch"):
+ *   [0] 1 = the launch hands over, [1] segments per frame, [2] first level-S row of the lower segment (0: not the two-segment
+ *   geometry; no ranges then), [3] strips per frame,
+ *   [4] / [5] (frame, strip) pairs that took the hand-off / marched on without it in the LAST float64 launch of this context
+ *   (counted only under "dc_stitch_count" 1; read after the work queued on `stream`),
+ *   [6] the per-frame override in force ("dc_stitch_stall_frame"; -1 none), [7] reserved,
+ *   [8 + 6 k .. 8 + 6 k + 5], k = 0 .. S: inclusive row ranges at level k (0 = the input): rows the upper wave reads or computes
+ *   itself (first, last), rows it takes from the hand-off (first, last; first > last: none), rows the lower wave reads or emits.
+ * S = 0: the counters only.  ctx = NULL: a host-only query that needs no device -- the four switches are read from out_host[0 .. 3]
+ * ("dc_segs", "dc_wpg", "dc_split", "dc_stitch") before it is filled, and no counters are reported. */
+#define RM_CHAIN_STITCH_WORDS 64
+int rm_debug_chain_stitch(rm_ctx *ctx, int S, int H, int W, int T, long long *out_host, void *stream);
+
 /* a copy of the first `bytes` bytes of the context's workspace buffer `name` as the last call left it ("tile_lo", "tile_hi": the
  * [unique frame][tile] bounds of the selection; "cS": the collapsed band-passed level) -- tests check the bounds themselves with it */
 int rm_debug_workspace(rm_ctx *ctx, const char *name, void *out_host, size_t bytes, void *stream);

@@ -127,6 +127,10 @@ extern "C" int rm_debug_set(rm_ctx *ctx, const char *key, long long value)
     else if (k == "dc_segs") d.dc_segs = (int)value;
     else if (k == "dc_wpg") d.dc_wpg = (int)value;
     else if (k == "dc_split") d.dc_split = (int)value;
+    else if (k == "dc_stitch") d.dc_stitch = (int)value;
+    else if (k == "dc_stitch_count") d.dc_stitch_count = (int)value;
+    else if (k == "dc_stitch_swap") d.dc_stitch_swap = (int)value;
+    else if (k == "dc_stitch_stall_frame") d.dc_stitch_stall_frame = (int)value;
     else if (k == "dc_prio") d.dc_prio = (int)value;
     else if (k == "dc_prio_shift") d.dc_prio_shift = (int)value;
     else if (k == "store_slots") d.store_slots = value;

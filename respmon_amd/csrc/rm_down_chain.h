@@ -45,7 +45,58 @@ struct DownGeom {
                                      // developer settings: 0 none, 1 static (younger workgroups higher), 3 static (older higher)
     int prio_shift;                  // log2 of the rotation period in input rows (4: measured 16 / 32 / 64 / 128 rows in one process, tools/ab_inproc.py -- 0.6817 / 0.6837 / 0.6848 / 0.6883 ms against 0.7028 without priorities)
     int prio_rank;                   // dispatch-order quartile of this workgroup (0 = oldest), set by the kernel
+    // hand-off of the segment boundary (two segments, float64 DPP front end, S = 2..4; "the stitch", see DownChain::run): the lower wave
+    // leaves its first three rows of every level 1..S-1 in `hand`, the upper wave stops reading input three rows into the lower
+    // segment's range and feeds those rows into its cascade instead of deriving them from 2^(S+1) + 2^S - 6 more input rows
+    int stitch;                      // 1: this launch hands over (decided on the host: make_down_geom + launch_down_chain_t)
+    int stitch_swap;                 // 1: the LOWER segment sits on the even XCD (test hook: the host emulation runs blocks in index order)
+    int stitch_stall;                // > 0: the lower wave of frame stitch_stall - 1, strip 0 withholds its flag (test hook: a mixed workgroup)
+    unsigned stitch_epoch;           // value of a set flag in this launch (never 0; flags of earlier launches hold earlier epochs)
+    double *hand;                    // [frame][strip][level 1..S-1][row 0..2][q][lane]
+    unsigned *hand_flag;             // [frame][strip] one flag per 128-byte line
+    unsigned *hand_count;            // nullptr, or [2][DC_COUNT_STRIPES]: (frame, strip) pairs that injected / fell back
 };
+
+constexpr int DC_FLAG_STRIDE = 32;     // unsigned words between two hand-off flags: a 128-byte line each
+constexpr int DC_COUNT_STRIPES = 64;
+
+// first row of level k (k = S .. 0) in the dependency cone of level-S row s with no image border in the way: where the LOWER segment
+// starts.  One definition for the kernel, the host geometry and the debug entry.
+__host__ __device__ inline void dc_lower_first(int S, int s, int *nl)
+{
+    nl[S] = s;
+    for (int k = S - 1; k >= 0; --k) nl[k] = 2 * nl[k + 1] - 2;
+}
+
+// The hand-off travels between two XCDs whose L2s are not coherent: the payload and the flag are written through (sc1) as relaxed
+// agent-scope atomics on global addresses and read the same way; see DownChain::publish / decide for the ordering around them.
+#ifdef RM_HIPEMU
+__device__ __forceinline__ void dc_store_wt(double *p, double v) { *p = v; }
+__device__ __forceinline__ double dc_load_wt(const double *p) { return *p; }
+__device__ __forceinline__ void dc_store_flag(unsigned *p, unsigned v) { *p = v; }
+__device__ __forceinline__ unsigned dc_load_flag(const unsigned *p) { return *p; }
+__device__ __forceinline__ void dc_drain_stores() {}
+__device__ __forceinline__ void dc_acquire() {}
+#else
+typedef __attribute__((address_space(1))) unsigned long long dc_gu64;
+typedef __attribute__((address_space(1))) unsigned int dc_gu32;
+__device__ __forceinline__ void dc_store_wt(double *p, double v)
+{
+    __hip_atomic_store((dc_gu64 *)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double dc_load_wt(const double *p)
+{
+    return __longlong_as_double((long long)__hip_atomic_load((dc_gu64 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+__device__ __forceinline__ void dc_store_flag(unsigned *p, unsigned v) { __hip_atomic_store((dc_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned dc_load_flag(const unsigned *p) { return __hip_atomic_load((dc_gu32 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void dc_drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ void dc_acquire()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+#endif
 
 // compile-time strip width (level-S columns) per chain depth: level-0 span stays <= ~380 pixels
 #ifndef RM_DC_SW4
@@ -76,6 +127,10 @@ template <int S, int SW, int V> struct DCLayout {
     static constexpr int rowbuf_size(int k) { return 2 * half(k); }
     static constexpr int rowbuf_off(int k) { int o = 0; for (int i = 0; i < k; ++i) o += rowbuf_size(i); return o; }
     static constexpr int total() { return rowbuf_off(S); }
+    // hand-off block of one (frame, strip): three rows of nq(k) x 64 doubles for every level k = 1..S-1 (every lane stores and reads
+    // back its own elements: the two waves of a strip have the same lane <-> column map)
+    static constexpr int hand_off(int k) { int o = 0; for (int i = 1; i < k; ++i) o += 3 * 64 * nq(i); return o; }
+    static constexpr int hand_total() { return hand_off(S); }
 };
 
 // whole-wave shift by one lane (DPP wave_shr:1 / wave_shl:1): lane i receives lane i-1 / i+1;
@@ -185,12 +240,15 @@ template <typename LL, int S> struct VState<LL, S, S> {};
 // VB = false: hot instantiation, valid when every level has >= 3 rows: steady-state vertical pass plus two
 // uniform special cases at the image top and virtual (replayed) rows at the image bottom;
 // VB = true: fully generic form (any size, incl. 1- and 2-row levels), used for tiny images only.
-template <typename Tin, int S, bool VB>
+// ST = true: the instantiation that can hand the segment boundary over (k_down_chain_stitch); with ST = false none of that code exists
+template <typename Tin, int S, bool VB, bool ST = false>
 struct DownChain {
     static constexpr int SW = StripWidth<S>::SW;
     static constexpr int V = VecTraits<Tin>::V;
     using L = DCLayout<S, SW, V>;
     static constexpr int NL = L::nl();
+    static constexpr bool kStitch = ST;
+    static_assert(!ST || (V == 2 && !VB && S >= 2 && S <= 4), "the hand-off exists for the hot float64 chain of depth 2..4");
 
     const DownGeom &g;
     double *lds;
@@ -206,6 +264,11 @@ struct DownChain {
     int col1_lane;               // level-1 column of this lane's q = 0 element
     int q1;                      // level-1 columns between consecutive q (64; 62 on the register/DPP front end)
     bool lane_ok1;               // this lane's level-1 elements are real (DPP front end: lanes 1..62)
+    // hand-off of the segment boundary (g.stitch): wave-uniform, and few -- the kernel has no scalar register to spare
+    bool save_on;                // this is the lower wave of a stitched launch: emit() leaves rows nl(k) .. nl(k) + 2 of levels 1..S-1 in memory
+    bool sync_on = true;         // lockstep() still holds (off behind the upper workgroup's look at the flags)
+    int stop_row = -1;           // upper wave of a stitched launch: the input row behind which it looks at the flags (nl(0) + 2)
+    int pair_id;                 // frame * strips + strip: which hand-off block and flag are this wave's
     VState<L, S, 0> vs;
 
     __device__ __forceinline__ DownChain(const DownGeom &g_, double *lds_) : g(g_), lds(lds_), lane(threadIdx.x & 63) {}
@@ -215,7 +278,94 @@ struct DownChain {
     // in L2 for the neighbour.  Raw s_barrier: no waitcnt, the prefetched rows stay in flight across it.
     __device__ __forceinline__ void lockstep() const
     {
-        if (g.wpg > 1) __builtin_amdgcn_s_barrier();
+        if (g.wpg > 1 && (!kStitch || sync_on)) __builtin_amdgcn_s_barrier();
+    }
+
+    // ---- hand-off of the segment boundary ----------------------------------------------------------------
+    // the lower segment's first row of level k (dc_lower_first in closed form: nl(k) - 2 = 2 (nl(k+1) - 2))
+    __device__ __forceinline__ int nl(int k) const { return ((g.seg_split - 2) << (S - k)) + 2; }
+    __device__ __forceinline__ double *hand_blk() const { return g.hand + (size_t)pair_id * L::hand_total() + lane; }
+    __device__ __forceinline__ unsigned *flag_blk() const { return g.hand_flag + (size_t)pair_id * DC_FLAG_STRIDE; }
+    // LOWER wave, from emit<K>: row y of level K + 1 (values x, already scaled) is one of its first three -> written through to the
+    // hand-off block.  Behind the last of them (row nl[S-1] + 2) the wave drains its stores and one lane sets the flag: the payload
+    // is in memory before the flag is.
+    template <int K> __device__ __forceinline__ void publish(int y, const double (&x)[L::nq(K + 1)])
+    {
+        const int rel = y - nl(K + 1);
+        if ((unsigned)rel < 3u) {
+            double *dst = hand_blk() + L::hand_off(K + 1) + rel * (64 * L::nq(K + 1));
+#pragma unroll
+            for (int q = 0; q < L::nq(K + 1); ++q) dc_store_wt(dst + 64 * q, x[q]);
+            if (K + 2 == S && rel == 2) {
+                dc_drain_stores();
+                if (lane == 0 && g.stitch_stall * g.strips != pair_id + g.strips) dc_store_flag(flag_blk(), g.stitch_epoch);   // (test hook: frame stitch_stall - 1, strip 0 keeps it back)
+            }
+        }
+    }
+
+    // UPPER workgroup, once, behind input row stop_row: has the lower wave of every strip of this workgroup set its flag?  One
+    // decision per workgroup (wave 0 looks at both flags, LDS, one barrier): lockstep() counts every live wave, so two waves that
+    // disagreed would hang.  No barrier follows in either branch.  The look never waits: flags not set = march on as before.
+    __device__ __forceinline__ bool decide()
+    {
+        bool ok = true;
+        const bool wave0 = (threadIdx.x >> 6) == 0;
+        if (wave0) {
+            ok = dc_load_flag(flag_blk()) == g.stitch_epoch;
+            if (g.wpg > 1 && pair_id % g.strips + 1 < g.strips) ok = (dc_load_flag(flag_blk() + DC_FLAG_STRIDE) == g.stitch_epoch) && ok;
+            dc_acquire();   // no earlier load of this CU may serve the payload
+        }
+        if (g.wpg > 1) {
+            int *word = reinterpret_cast<int *>(lds - (threadIdx.x >> 6) * L::total());   // wave 0's slice: its level-0 row buffer is unused on the DPP front end
+            if (wave0 && lane == 0) *word = ok ? 1 : 0;
+            __syncthreads();
+            ok = *word != 0;
+        }
+        sync_on = false;
+        if (g.hand_count && lane == 0) atomicAdd(g.hand_count + (ok ? 0 : DC_COUNT_STRIPES) + (blockIdx.x & (DC_COUNT_STRIPES - 1)), 1u);
+        return ok;
+    }
+
+    // UPPER wave: rows nl(K) .. nl(K) + 2 of level K come from the hand-off block (what emit<K - 1> would have put into row buffer K,
+    // bit for bit: same inputs, same operations) and run down the cascade; then the next level's.  All 3 (S - 1) rows are asked for
+    // at once, before the first is used: one memory latency at the end of the wave's life instead of one per row (the registers
+    // of the input prefetch are free by then).
+    template <int K, int End = S> struct HandRows : HandRows<K + 1, End> { double x[3][L::nq(K)]; };
+    template <int End> struct HandRows<End, End> {};
+    template <int K> __device__ __forceinline__ void fetch_hand(HandRows<1> &hr)
+    {
+        HandRows<K> &h = hr;
+        const double *src = hand_blk() + L::hand_off(K);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int q = 0; q < L::nq(K); ++q) h.x[i][q] = dc_load_wt(src + 64 * (i * L::nq(K) + q));
+        }
+        if constexpr (K + 1 < S) fetch_hand<K + 1>(hr);
+    }
+    template <int K> __device__ __forceinline__ void inject(HandRows<1> &hr)
+    {
+        constexpr int NQ = L::nq(K);
+        HandRows<K> &h = hr;
+        const int qs = (K == 1) ? q1 : 64;
+        const bool ok = (K == 1) ? lane_ok1 : true;
+#pragma nounroll
+        for (int i = 0; i < 3; ++i) {
+            if (ok) {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) rowdst[K][(qs >> 1) * q] = h.x[0][q];
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) { h.x[0][q] = h.x[1][q]; h.x[1][q] = h.x[2][q]; }   // the next row moves up: no indexed registers
+            wave_sync();
+            make_border<K>();
+            wave_sync();
+            double n[L::nq(K + 1)];
+            taps<K>(n);
+            wave_sync();
+            feed<K>(nl(K) + i, n);
+        }
+        if constexpr (K + 1 < S) inject<K + 1>(hr);
     }
 
     // index of column c inside row buffer K (columns c0-2 .. are stored de-interleaved)
@@ -259,9 +409,15 @@ struct DownChain {
                 if (ok && cq >= cx0[S] && cq <= cx1[S]) out_frame[(size_t)y * g.w[S] + cq] = v[q] * (1.0 / 256);
             }
         } else {
+            double x[L::nq(K + 1)];
+#pragma unroll
+            for (int q = 0; q < L::nq(K + 1); ++q) x[q] = v[q] * (1.0 / 256);
+            if constexpr (kStitch) {
+                if (save_on) publish<K>(y, x);   // wave-uniform side effect: stores only, the vertical state is not touched
+            }
             if (ok) {
 #pragma unroll
-                for (int q = 0; q < L::nq(K + 1); ++q) rowdst[K + 1][(qs >> 1) * q] = v[q] * (1.0 / 256);  // +qs columns: same parity
+                for (int q = 0; q < L::nq(K + 1); ++q) rowdst[K + 1][(qs >> 1) * q] = x[q];  // +qs columns: same parity
             }
             wave_sync();
             make_border<K + 1>();
@@ -426,8 +582,10 @@ struct DownChain {
     // Chunk q covers columns P + 124*q + [0,128): consecutive chunks overlap by two lanes so that lanes
     // 1..62 of every chunk own 62 consecutive level-1 columns and lanes 0 / 63 only provide halo.
     // PL / PR: the first / last chunk of a row holds columns a neighbouring strip reads too -> plain (cache-allocating) loads there
+    // Returns true when the march stopped behind stop_row because the hand-off is there (the caller injects); otherwise the whole
+    // range has been marched.
     template <bool PL, bool PR>
-    __device__ __forceinline__ void run_dpp(const Tin *frame, int p_first, int p_last)
+    __device__ __forceinline__ bool run_dpp(const Tin *frame, int p_first, int p_last)
     {
         constexpr int NQ1 = L::nq(1);
         const int W = g.w[0];
@@ -486,24 +644,32 @@ struct DownChain {
                 n[q] = a * 6 + (b_prev + b) * 4 + a_prev + a_next;
             }
         };
+        // An upper wave of a stitched launch marches to stop_row only (and asks for nothing behind it), then looks at the flags: set ->
+        // the caller injects; not set -> a SECOND TRIP of the same loop marches on to p_last.  Every other wave makes one trip.
+        int p_begin = p_first, p_end = (kStitch && stop_row >= 0) ? stop_row : p_last;
         Raw16 regs[DC_PREFETCH][NQ1];
-#pragma unroll
-        for (int i = 0; i < DC_PREFETCH; ++i) issue(min(p_first + i, p_last), regs[i]);
         if (g.prio == 1) dc_set_prio(g.prio_rank);
         else if (g.prio == 3) dc_set_prio(3 - g.prio_rank);
-        for (int base = p_first; base <= p_last; base += DC_PREFETCH) {
-            if (g.prio == 2 && ((base - p_first) & ((1 << g.prio_shift) - 1)) == 0) dc_set_prio(g.prio_rank + ((base - p_first) >> g.prio_shift));
-            lockstep();
+        for (;;) {
 #pragma unroll
-            for (int i = 0; i < DC_PREFETCH; ++i) {
-                const int p = base + i;
-                if (p <= p_last) {
-                    double n[NQ1];
-                    hrow(regs[i], n);
-                    issue(min(p + DC_PREFETCH, p_last), regs[i]);
-                    feed<0>(p, n);
+            for (int i = 0; i < DC_PREFETCH; ++i) issue(min(p_begin + i, p_end), regs[i]);
+            for (int base = p_begin; base <= p_end; base += DC_PREFETCH) {
+                if (g.prio == 2 && ((base - p_first) & ((1 << g.prio_shift) - 1)) == 0) dc_set_prio(g.prio_rank + ((base - p_first) >> g.prio_shift));
+                lockstep();
+#pragma unroll
+                for (int i = 0; i < DC_PREFETCH; ++i) {
+                    const int p = base + i;
+                    if (p <= p_end) {
+                        double n[NQ1];
+                        hrow(regs[i], n);
+                        issue(min(p + DC_PREFETCH, p_end), regs[i]);
+                        feed<0>(p, n);
+                    }
                 }
             }
+            if (!kStitch || p_end == p_last) return false;
+            if (decide()) return true;
+            p_begin = p_end + 1; p_end = p_last;
         }
     }
 
@@ -569,7 +735,7 @@ struct DownChain {
         }
     }
 
-    __device__ __forceinline__ void run(const Tin *frame, double *out_t, int strip, int seg)
+    __device__ __forceinline__ void run(const Tin *frame, double *out_t, int t, int strip, int seg)
     {
         // ranges, from level S back to 0
         cx0[S] = strip * g.sw; cx1[S] = min(cx0[S] + g.sw, g.w[S]) - 1;
@@ -590,10 +756,23 @@ struct DownChain {
         lane_ok1 = dpp ? (lane >= 1 && lane <= 62) : true;
         out_frame = out_t;
         setup_level<0>();
+        save_on = false;
+        if constexpr (kStitch) {
+            // Hand-off of the segment boundary.  With nl[k] the lower segment's first row of level k, the upper wave reads input rows
+            // up to nl[0] + 2 only (three rows shared with the lower wave instead of 2^(S+1) + 2^S - 3); by then its cascade has
+            // produced level-k rows up to nl[k] - 1 (k = 1) resp. less (k > 1) by itself.  Rows nl[1] .. nl[1] + 2 of level 1 come from
+            // the lower wave and complete level 2 up to nl[2] - 1, the three handed-over rows of level 2 complete level 3, and so on: the
+            // three rows of level S-1 complete level S up to seg_split - 1, the upper segment's range.  (g.stitch implies dpp.)
+            if (g.stitch) {
+                pair_id = t * g.strips + strip;
+                save_on = seg != 0;
+                if (seg == 0) stop_row = nl(0) + 2;
+            }
+        }
         if constexpr (kF64) {
             if (dpp) {
 #ifdef RM_DC_ALL_STREAM
-                run_dpp<false, false>(frame, next[0], last[0]);
+                const bool inj = run_dpp<false, false>(frame, next[0], last[0]);
 #else
                 // wave-uniform choice, made once: inside the march the loads are straight-line code
 #if defined(RM_DC_POLICY_LEFT)
@@ -603,11 +782,20 @@ struct DownChain {
 #else
                 const bool pl = cx0[S] > 0, pr = cx1[S] < g.w[S] - 1;
 #endif
-                if (pl && pr) run_dpp<true, true>(frame, next[0], last[0]);
-                else if (pl) run_dpp<true, false>(frame, next[0], last[0]);
-                else if (pr) run_dpp<false, true>(frame, next[0], last[0]);
-                else run_dpp<false, false>(frame, next[0], last[0]);
+                bool inj;
+                if (pl && pr) inj = run_dpp<true, true>(frame, next[0], last[0]);
+                else if (pl) inj = run_dpp<true, false>(frame, next[0], last[0]);
+                else if (pr) inj = run_dpp<false, true>(frame, next[0], last[0]);
+                else inj = run_dpp<false, false>(frame, next[0], last[0]);
 #endif
+                if constexpr (kStitch) {
+                    if (inj) {
+                        HandRows<1> hr;
+                        fetch_hand<1>(hr);
+                        inject<1>(hr);
+                    }
+                }
+                (void)inj;
                 return;
             }
         }
@@ -619,10 +807,9 @@ template <typename Tin, int S> __host__ __device__ constexpr int down_chain_lds_
 
 constexpr int DC_MAX_WPG = 2;  // waves per workgroup (launch bound).  Measured in bench.py, 1080p x 256 f64: 1 -> 0.816 ms, 2 -> 0.788 ms, 3 -> 1.06 ms (a stalled wave stalls its whole group: fewer independent contexts per CU)
 
-template <typename Tin, int S, bool VB>
-__global__ __launch_bounds__(64 * DC_MAX_WPG) void k_down_chain(const Tin *frames, size_t frame_stride, DownGeom g, double *out)
+template <typename Tin, int S, bool VB, bool ST>
+__device__ __forceinline__ void down_chain_body(const Tin *frames, size_t frame_stride, DownGeom &g, double *out)
 {
-    RM_TRACE_SCOPE(0);
     HIP_DYNAMIC_SHARED(double, lds_all)
     // XCD-aware mapping: block b runs on XCD b % 8; give each XCD whole frames so the strips and
     // segments of a frame share halo lines in one L2.  A workgroup = g.wpg adjacent strips of one segment,
@@ -635,7 +822,7 @@ __global__ __launch_bounds__(64 * DC_MAX_WPG) void k_down_chain(const Tin *frame
         // odd XCDs of an MI355X stream ~4-5 % slower than the even ones (workgroup timelines, tools/trace_tail.py, on every
         // box measured), and with equal shares the launch waits for them while the even XCDs sit idle.
         const int pair = xcd >> 1;
-        seg = xcd & 1;
+        seg = ST ? (xcd & 1) ^ (g.stitch_swap & 1) : (xcd & 1);
         t = (j / groups) * 4 + pair;
         grp = j - (j / groups) * groups;
     } else {
@@ -650,8 +837,25 @@ __global__ __launch_bounds__(64 * DC_MAX_WPG) void k_down_chain(const Tin *frame
     if (strip >= g.strips) return;  // a terminated wave no longer counts at s_barrier
     double *lds = lds_all + wave * down_chain_lds_doubles<Tin, S>();
     g.prio_rank = dc_dispatch_quartile();
-    DownChain<Tin, S, VB> dc(g, lds);
-    dc.run(frames + (size_t)t * frame_stride, out + (size_t)t * g.h[S] * g.w[S], strip, seg);
+    DownChain<Tin, S, VB, ST> dc(g, lds);
+    dc.run(frames + (size_t)t * frame_stride, out + (size_t)t * g.h[S] * g.w[S], t, strip, seg);
+}
+
+template <typename Tin, int S, bool VB>
+__global__ __launch_bounds__(64 * DC_MAX_WPG) void k_down_chain(const Tin *frames, size_t frame_stride, DownGeom g, double *out)
+{
+    RM_TRACE_SCOPE(0);
+    down_chain_body<Tin, S, VB, false>(frames, frame_stride, g, out);
+}
+
+// the float64 chain of a launch that hands its segment boundary over (g.stitch): a kernel of its own, so that every other launch runs
+// the code it ran before the hand-off existed
+static_assert(DC_MAX_WPG <= 2, "DownChain::decide looks at the flags of at most two strips");
+template <int S>
+__global__ __launch_bounds__(64 * DC_MAX_WPG) void k_down_chain_stitch(const double *frames, size_t frame_stride, DownGeom g, double *out)
+{
+    RM_TRACE_SCOPE(0);
+    down_chain_body<double, S, false, true>(frames, frame_stride, g, out);
 }
 
 // host-side geometry
@@ -686,11 +890,29 @@ inline bool down_chain_hot_ok(int S, const int *h)
 
 // geometry of one launch over level-S rows [y_begin, y_end)
 // force_segs / force_wpg / split_permille > 0: developer overrides (rm_debug_set "dc_segs" / "dc_wpg" / "dc_split")
+// stitch: 1 = a float64 launch on the DPP front end that may hand the boundary of its two segments over (g.stitch says whether it does)
+// upper segment's share of the level-S rows: halo path / stitched launches.  A stitched upper wave reads 42 input rows less at depth 4,
+// so the boundary moves down one level-S row at 1080p (35 -> 36 of 68).  Measured in one process on one buffer, 256 x 1080p float64
+// (tools/ab_inproc.py, six rounds, profiles/chain_stitch.json): halo path 0.8290 / 0.8291 ms per step, stitched at 513 per mille
+// 0.8227, at 530 0.8188.
+constexpr double DC_SPLIT_HALO = 0.513, DC_SPLIT_STITCH = 0.530;
+
+inline bool down_chain_can_stitch(const DownGeom &g, bool tiny)
+{
+    if (g.S < 2 || g.S > 4 || g.seg_split <= 0 || tiny || !g.vec || !down_chain_hot_ok(g.S, g.h)) return false;
+    // every handed-over row, and every row the two waves derive from or with them, lies inside the dependency cone of level-S row
+    // seg_split: no image-border rule (reflection at the top, replayed rows at the bottom) may touch that cone
+    int y0, y1;
+    down_chain_interior(g.S, g.h, &y0, &y1);
+    return g.seg_split >= y0 && g.seg_split < y1 && g.seg_split - 1 >= g.y_begin && g.seg_split < g.y_end;
+}
+
 inline bool make_down_geom(int S, const int *h, const int *w, int T, int vec_ok, int y_begin, int y_end, DownGeom &g, bool tiny = false,
-                           int force_segs = 0, int force_wpg = 0, int split_permille = 0)
+                           int force_segs = 0, int force_wpg = 0, int split_permille = 0, int stitch = 0)
 {
     if (S < 1 || S > 5 || y_end <= y_begin) return false;
     g.S = S; g.T = T; g.vec = vec_ok; g.y_begin = y_begin; g.y_end = y_end; g.prio = 0; g.prio_rank = 0; g.prio_shift = 4;
+    g.stitch = 0; g.stitch_swap = 0; g.stitch_stall = 0; g.stitch_epoch = 0; g.hand = nullptr; g.hand_flag = nullptr; g.hand_count = nullptr;
     for (int k = 0; k <= S; ++k) { g.h[k] = h[k]; g.w[k] = w[k]; }
     const int SW = S == 1 ? StripWidth<1>::SW : S == 2 ? StripWidth<2>::SW : S == 3 ? StripWidth<3>::SW
                  : S == 4 ? StripWidth<4>::SW : StripWidth<5>::SW;
@@ -714,11 +936,17 @@ inline bool make_down_geom(int S, const int *h, const int *w, int T, int vec_ok,
     if (tiny) g.seg_h = rows < 2 ? rows : 2;  // test hook: many small segments
     g.segs = (rows + g.seg_h - 1) / g.seg_h;
     // exactly two segments: split them 51.3 : 48.7 between an even XCD and its (slower) odd neighbour, see k_down_chain
+    // (a stitched launch has its own share: its upper segment reads 2^(S+1) + 2^S - 6 input rows less.  Whether a launch can stitch
+    // depends on where the boundary falls, so the stitched share is tried first and the halo path keeps its own.)
     g.seg_split = 0;
-    if (g.segs == 2 && !tiny && rows >= 8) {
-        int upper = (int)(rows * (split_permille > 0 ? split_permille * 0.001 : 0.513) + 0.5);
-        if (upper >= rows) upper = rows - 1;
-        if (upper > g.seg_h) g.seg_split = y_begin + upper;
+    for (int pass = stitch ? 0 : 1; pass < 2 && !g.stitch; ++pass) {
+        g.seg_split = 0;
+        if (g.segs == 2 && !tiny && rows >= 8) {
+            int upper = (int)(rows * (split_permille > 0 ? split_permille * 0.001 : pass == 0 ? DC_SPLIT_STITCH : DC_SPLIT_HALO) + 0.5);
+            if (upper >= rows) upper = rows - 1;
+            if (upper > g.seg_h) g.seg_split = y_begin + upper;
+        }
+        if (pass == 0) g.stitch = down_chain_can_stitch(g, tiny) ? 1 : 0;
     }
     // workgroup = up to DC_MAX_WPG adjacent strips in lockstep, split evenly when a row has more strips
     const int ngroups = (g.strips + DC_MAX_WPG - 1) / DC_MAX_WPG;
@@ -728,6 +956,29 @@ inline bool make_down_geom(int S, const int *h, const int *w, int T, int vec_ok,
 #endif
     if (force_wpg >= 1 && force_wpg <= DC_MAX_WPG) g.wpg = force_wpg;
     return true;
+}
+
+// Row ranges (inclusive) of the two segments of a seg_split geometry at every level k = 0..S, as DownChain::run walks them: rows the
+// upper wave reads (k = 0) or computes itself, rows it takes from the hand-off (first > last: none), rows the lower wave reads or
+// emits.  The arithmetic the kernel uses (dc_lower_first, the 2y - 2 .. 2y + 2 cones), in one place a test can call.
+struct DownRanges { int up_first[MAX_CHAIN], up_last[MAX_CHAIN], inj_first[MAX_CHAIN], inj_last[MAX_CHAIN], lo_first[MAX_CHAIN], lo_last[MAX_CHAIN]; };
+inline void down_chain_ranges(const DownGeom &g, DownRanges &r)
+{
+    const int S = g.S;
+    r.up_first[S] = g.y_begin; r.up_last[S] = g.seg_split - 1; r.lo_first[S] = g.seg_split; r.lo_last[S] = g.y_end - 1;
+    for (int k = S - 1; k >= 0; --k) {
+        r.up_first[k] = 2 * r.up_first[k + 1] - 2 > 0 ? 2 * r.up_first[k + 1] - 2 : 0;
+        r.lo_first[k] = 2 * r.lo_first[k + 1] - 2 > 0 ? 2 * r.lo_first[k + 1] - 2 : 0;
+        r.up_last[k] = 2 * r.up_last[k + 1] + 2 < g.h[k] - 1 ? 2 * r.up_last[k + 1] + 2 : g.h[k] - 1;
+        r.lo_last[k] = 2 * r.lo_last[k + 1] + 2 < g.h[k] - 1 ? 2 * r.lo_last[k + 1] + 2 : g.h[k] - 1;
+    }
+    for (int k = 0; k <= S; ++k) { r.inj_first[k] = 0; r.inj_last[k] = -1; }
+    if (g.stitch) {
+        int nl[MAX_CHAIN];
+        dc_lower_first(S, g.seg_split, nl);
+        r.up_last[0] = nl[0] + 2;
+        for (int k = 1; k < S; ++k) { r.up_last[k] = nl[k] - 1; r.inj_first[k] = nl[k]; r.inj_last[k] = nl[k] + 2; }
+    }
 }
 
 }  // namespace rm

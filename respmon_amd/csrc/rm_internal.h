@@ -111,6 +111,10 @@ struct DebugKnobs {
     int dc_prio_shift = 0;        // 1 .. 12: log2 of the rotation period of dc_prio 2 in input rows (default 4)
     int dc_prio = 2;              // k_down_chain: issue priority of its waves (2 rotating -- the default --, 0 none, 1 younger workgroups higher, 3 older higher)
     int dc_split = 0;             // > 0: share (per mille) of the level-S rows the upper of exactly two segments takes (default 513)
+    int dc_stitch = 1;            // k_down_chain<double>: 1 = a two-segment launch hands the segment boundary over as level rows where its geometry allows (rm_down_chain.h DownGeom::stitch), 0 = the halo path
+    int dc_stitch_count = 0;      // 1: the upper waves count the (frame, strip) pairs that injected / fell back (rm_debug_chain_stitch); off by default: 1 536 atomics at the end of the kernel cost more than the hand-off gains
+    int dc_stitch_swap = 0;       // 1: the lower segment on the even XCD (test hook: the host emulation runs the blocks in index order, so only then has the lower wave written when the upper one looks)
+    int dc_stitch_stall_frame = -1;   // >= 0: the lower wave of this frame, strip 0 withholds its flag (test hook: a workgroup whose strips disagree)
     int collapse_fused = 0;       // 1: collapse passes without a value store wherever TileEval applies (rm_tile_eval.h k_eval_c + k_dense_sum_t); 0: only as the stand-in for an overflowing store at skip >= 3
     long long label_host_steps = 0;   // > 0: border steps of an unlabelled host stage beyond which the next extraction is labelled on the device (default LABEL_MIN_STEPS)
     int ccl_tiles = 1;            // 0: rows of whole words labelled through global memory as the others are (k_ccl_union / k_ccl_bbox), not tile by tile in LDS
@@ -197,6 +201,8 @@ struct rm_ctx {
     int *h_flag = nullptr;          // pinned: {overflow flag, largest per-rank tile count} of the sparse heatmap merge
     void *comm = nullptr; int comm_rank = 0, comm_world = 1;   // RCCL communicator (rm_comm_init); none: one rank
     ExchangeState xp_streams, xp_sharded;
+    // hand-off of the frame-buffer kernel's segment boundary (rm_down_launch.h): the value a set flag holds in the next launch, and the flag buffer that was zeroed for it
+    unsigned dc_epoch = 0; const void *dc_flags_seen = nullptr; size_t dc_flags_cap = 0; bool dc_counted = false;
     int refine_hint = 0;            // the last rm_locate of this context kept many pairs at skip >= 3: the next one refines its bounds one level down (rm_bounds_l1.h k_bounds_up1)
     int dense_hint = 0;             // the last rm_locate of this context met a dense selection (more than a quarter of the pairs kept)
     long long store_hint_slots = 0; // slots a selection of this context needed when it overflowed the value store (rm_locate grows the store to it)

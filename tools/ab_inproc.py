@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--steps", type=int, default=150)
     ap.add_argument("--video", default="breathing")
+    ap.add_argument("--json", default=None, help="also write the rounds and medians to this file")
     ap.add_argument("combos", nargs="+")
     a = ap.parse_args()
     T, H, W, L, S, dt = bench.CONFIGS[a.config]
@@ -70,7 +71,7 @@ def main():
     for c in combos:
         for kv in c.split(","):
             if "=" in kv and kv.split("=")[0] not in defaults:
-                defaults[kv.split("=")[0]] = {"dc_prio": 2, "dc_prio_shift": 0, "heat_rows": 1, "ff_parts": 0, "dc_split": 0, "dc_segs": 0}.get(kv.split("=")[0], 0)
+                defaults[kv.split("=")[0]] = {"dc_prio": 2, "dc_prio_shift": 0, "heat_rows": 1, "ff_parts": 0, "dc_split": 0, "dc_segs": 0, "dc_stitch": 1, "dc_stitch_stall_frame": -1}.get(kv.split("=")[0], 0)
 
     def step():
         return be.locate(buf, 10, 0.1, 1.0, 500, L, S, 0.7, 20, 0)
@@ -78,13 +79,14 @@ def main():
     t0 = time.perf_counter(); step(); torch.cuda.synchronize(); one = time.perf_counter() - t0
     for _ in range(int(min(600, max(10, 0.7 / max(one, 1e-5))))):
         step()
-    res = {c: [] for c in combos}
-    rois = {}
+    # keyed by position: the same setting given twice is an A/A pair (the run's own noise)
+    res = [[] for _ in combos]
+    rois = [None] * len(combos)
     for r in range(a.rounds):
-        for c in combos:
+        for ci, c in enumerate(combos):
             apply(c)
             for _ in range(5):
-                rois[c] = step()
+                rois[ci] = step()
             torch.cuda.synchronize()
             _capi.check(lib, lib.rm_profile_enable(ctx, 1), "profile")
             t0 = time.perf_counter()
@@ -95,11 +97,19 @@ def main():
             pm = (ctypes.c_double * 4)(); n = ctypes.c_int()
             _capi.check(lib, lib.rm_profile_read(ctx, pm, ctypes.byref(n)), "profile_read")
             _capi.check(lib, lib.rm_profile_enable(ctx, 0), "profile")
-            res[c].append((ms, pm[0] / max(n.value, 1)))
-    for c in combos:
-        ms = np.array(res[c])
-        print("%-44s step ms %s  median %.4f | kernel ms median %.4f | roi %s" % (c, " ".join("%.4f" % v for v in ms[:, 0]), np.median(ms[:, 0]),
-                                                                                 np.median(ms[:, 1]), rois[c]))
+            res[ci].append((ms, pm[0] / max(n.value, 1)))
+    out = []
+    for ci, c in enumerate(combos):
+        ms = np.array(res[ci])
+        print("%-44s step ms %s  median %.4f | kernel ms %s  median %.4f | roi %s" % (c, " ".join("%.4f" % v for v in ms[:, 0]), np.median(ms[:, 0]),
+                                                                                     " ".join("%.4f" % v for v in ms[:, 1]), np.median(ms[:, 1]), rois[ci]))
+        out.append({"setting": c, "step_ms": [round(float(v), 5) for v in ms[:, 0]], "kernel_ms": [round(float(v), 5) for v in ms[:, 1]],
+                    "step_ms_median": round(float(np.median(ms[:, 0])), 5), "kernel_ms_median": round(float(np.median(ms[:, 1])), 5),
+                    "roi": list(rois[ci]) if rois[ci] is not None else None})
+    if a.json:
+        import json
+        with open(a.json, "w") as f:
+            json.dump({"config": a.config, "in_dtype": dt, "rounds": a.rounds, "steps": a.steps, "settings": out}, f, indent=1)
 
 
 if __name__ == "__main__":

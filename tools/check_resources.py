@@ -19,7 +19,7 @@ DEFAULT = os.path.join(ROOT, "respmon_amd", "csrc", "build_resources.txt")
 # ... and the live stream (rm_stream.hip): k_sosfilt keeps the 2 x nsec state values of its element in registers over a whole call, and the
 #     SYM = 0 instances of k_magnify (one frame tile in flight) fall under the k_magnify pattern with the SYM = 1 ones
 # ... and the multi-subject ROI mean (rm_subjects.h): a workgroup per (frame, subject) pair streams its rectangle once
-MUST_NOT_SPILL = re.compile(r"^(void )?rm::k_down_chain<[^>]*, false>|^(void )?rm::k_down_chain_u8<|^(void )?rm::k_down_chain_narrow<|"
+MUST_NOT_SPILL = re.compile(r"^(void )?rm::k_down_chain<[^>]*, false>|^(void )?rm::k_down_chain_stitch<|^(void )?rm::k_down_chain_u8<|^(void )?rm::k_down_chain_narrow<|"
                             r"^(void )?rm::k_magnify<|^(void )?rm::k_roi_mean_multi_clip<|"
                             r"^(void )?rm::k_lk_track_multi_clip<|^(void )?rm::k_sosfilt<")
 # kernels (mangled names, as the report spells them) that may be compiled in more than one unit, each with its reason.  None: wherever
