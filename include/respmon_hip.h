@@ -356,6 +356,41 @@ int rm_window_locate_multi(rm_ctx *ctx, rm_window *win, double fps, double freq_
                            double temporal_threshold, int threshold, int max_rois, double min_area, int32_t *xywh_host,
                            double *area_host, int *n_host, void *stream);
 
+/* ---- the RATE MAP: for every pixel column the dominant frequency inside a band and the share of the band's power in that peak --
+ *      the estimator of prototypes/temporal_analysis.py (Blackman-Harris window, spectrum, argmax, parabolic(log .)) on a fine
+ *      frequency grid instead of the FFT bins, for every pixel of a pyramid level instead of one ROI signal.
+ *      Definition, x[T, NP] float64, 2 <= T <= 4096, 0 < freq_min < freq_max <= fps / 2, 3 <= nfreq = F <= 64:
+ *        step = (freq_max - freq_min) / (F - 1), f_j = freq_min + j * step;  w = scipy.signal.blackmanharris(T) (symmetric);
+ *        E[2j, t] = w[t] cos(2 pi f_j t / fps), E[2j+1, t] = -w[t] sin(2 pi f_j t / fps), A[r, t] = E[r, t] - mean_u E[r, u]
+ *        (sig - sig.mean() folded into the operator), built on the host in long double and rounded once;
+ *        y[t, p] = x[t, p] - x[0, p] (a column that never changes gives y == 0 exactly);
+ *        c_j = sum_t A[2j, t] y[t, p], s_j = sum_t A[2j+1, t] y[t, p] on v_mfma_f64_16x16x4_f64, P_j = c_j c_j + s_j s_j; the order
+ *        of the sums is the kernel's own and fixed for a given (T, NP, F);
+ *        total = sum_j P_j added in ascending j, index = the first j at which max_j P_j is reached, power = P_index;
+ *        total == 0: index = -1, freq = NaN, power = total = 0;
+ *        otherwise freq = f_index + delta * step, where for 0 < index < F - 1 and three positive powers a = log P_(index-1),
+ *        b = log P_index, c = log P_(index+1), num = a - c, den = (a - 2 b) + c, delta = den < 0 ? clamp((0.5 num) / den, -0.5, 0.5)
+ *        : 0, and delta = 0 elsewhere.
+ *      rm_spectral_operator (host only): A_host[2F][T] row major and freqs_host[F]; either may be NULL.
+ *      rm_spectral_peak: x_dev[T, NP]; outputs [NP] each, any may be NULL (not all).  Asynchronous on `stream`.
+ *      rm_rate_map: x = the Gaussian level `level` (1 <= level <= 5) of every frame of a frame buffer of any buffer dtype (RM_BGR8
+ *        included) -- what rm_pyr_down applied `level` times gives, bit for bit, written by the frame-buffer kernel in one pass over
+ *        the frames; outputs [h_level * w_level].  The level array lives in the context's workspace.
+ *      rm_window_rate_map: the same on the m = min(count, T) frames a window holds, read from the ring in place (the oldest frame is
+ *        x[0]); level = the window's skip_levels_at_top.  Bit for bit rm_rate_map on the contiguous buffer of those frames.
+ *      RM_E_BADARG: T < 2 (a window with count < 2), nfreq outside 3..64, a band that violates 0 < freq_min < freq_max <= fps / 2
+ *        (NaN included), all outputs NULL, NULL input, level < 1.  RM_E_UNSUPPORTED: T > 4096, level >= 6, a window whose rows are not
+ *        G_skip (RM_FLAG_FILTER_LAPLACIANS / RM_FLAG_UNFUSED_SMALL, or a geometry whose small pyramid is filtered level by level).
+ *        Nothing is written on a refusal.  rm_rate_map and rm_window_rate_map follow the RM_E_BUSY rule of rm_window_locate.
+ *      The operator is cached in the context per (T, fps, freq_min, freq_max, nfreq). */
+int rm_spectral_operator(int T, double fps, double freq_min, double freq_max, int nfreq, double *A_host, double *freqs_host);
+int rm_spectral_peak(rm_ctx *ctx, const double *x_dev, int T, size_t NP, double fps, double freq_min, double freq_max, int nfreq,
+                     double *freq_dev, double *power_dev, double *total_dev, int32_t *index_dev, void *stream);
+int rm_rate_map(rm_ctx *ctx, const void *frames_dev, int dtype, int T, int H, int W, int level, double fps, double freq_min,
+                double freq_max, int nfreq, double *freq_dev, double *power_dev, double *total_dev, int32_t *index_dev, void *stream);
+int rm_window_rate_map(rm_ctx *ctx, rm_window *win, double fps, double freq_min, double freq_max, int nfreq, double *freq_dev,
+                       double *power_dev, double *total_dev, int32_t *index_dev, void *stream);
+
 /* ---- a LIVE stream magnified chunk by chunk: the causal band-pass of rm_sosfilt with carried state.  rm_magnify's band-pass is
  *      the reference's FFT operator, which is even in time: its newest frame mixes in motion of the oldest frame of the buffer.  An
  *      rm_stream holds the filter state of every filtered pyramid element instead of a [T,H,W] buffer: each pushed chunk comes back

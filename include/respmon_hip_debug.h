@@ -27,7 +27,8 @@ extern "C" {
  * a small clip into several chunks: a chunk holds max(1, n / slot - 1) frames, slot = 5 bytes per pixel of every LK pyramid level of
  * the ROI -- for rm_flow_multi_clip the sum of that over the subjects that still have points.
  * "stream_frames" n: frames per internal chunk of rm_stream_push (0: by its workspace cap of 256 MiB, at most 256), so that a test
- * reaches the split with a handful of frames. */
+ * reaches the split with a handful of frames.
+ * "rate_wide" 0|1: the K-split / the wave-per-16-columns form of the rate map's kernel whatever the level size (-1: by size). */
 int rm_debug_set(rm_ctx *ctx, const char *key, long long value);
 
 /* counters of the last rm_calibrate on this context: out_host[0] = (frame, tile) pairs, [1] = pairs evaluated at full resolution

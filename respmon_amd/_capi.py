@@ -96,6 +96,10 @@ SIGNATURES = {
     "rm_window_locate": (_i, [_vp, _vp, _d, _d, _d, _d, _d, _i, _vp, _vp]),
     "rm_window_locate_multi": (_i, [_vp, _vp, _d, _d, _d, _d, _d, _i, _i, _d, _vp, _vp, _c.POINTER(_i), _vp]),
     "rm_debug_window_rows": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "rm_spectral_operator": (_i, [_i, _d, _d, _d, _i, _vp, _vp]),
+    "rm_spectral_peak": (_i, [_vp, _vp, _i, _sz, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "rm_rate_map": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "rm_window_rate_map": (_i, [_vp, _vp, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "rm_stream_create": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _d, _c.POINTER(_vp)]),
     "rm_stream_destroy": (_i, [_vp]),
     "rm_stream_reset": (_i, [_vp, _vp]),

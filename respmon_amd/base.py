@@ -26,7 +26,7 @@ from collections import deque
 
 import numpy as np
 
-from . import _capi, device
+from . import _capi, device, rate
 from .tools import Benchmarker, reduce_bounding_box
 from .measure import BreathSignal
 
@@ -718,6 +718,26 @@ class RespiratoryMonitor(BreathSignal):
             for roi in rois:
                 print('x:{0}, y:{1}, w:{2}, h:{3}'.format(*roi))
         return rois
+
+    @rate.static_or_instance
+    def rate_map(self, frames=None, fps=None, level=None, nfreq=64, freq_min=None, freq_max=None):
+        """How fast each part of the frame breathes: a rate.RateMap (bpm, periodicity, roi_bpm(roi)) at pyramid level `level` (default
+        4) -- the dominant frequency of the band per pixel and the share of the band's power in it (rm_rate_map).  On a monitor the
+        defaults are its calibration buffer, fps, freq_min and freq_max; RespiratoryMonitor.rate_map(frames, fps) is the static form,
+        like locate(), with the band of locate()'s defaults.  Feed roi_bpm the rectangles of locate_all()."""
+        if frames is None:
+            if self is None:
+                raise TypeError("RespiratoryMonitor.rate_map(frames, fps): the static form needs the frames")
+            frames = self.calibration_buffer
+        if fps is None:
+            if self is None:
+                raise TypeError("RespiratoryMonitor.rate_map(frames, fps): the static form needs fps")
+            fps = self.fps
+        if freq_min is None:
+            freq_min = self.freq_min if self is not None else 0.1
+        if freq_max is None:
+            freq_max = self.freq_max if self is not None else 1.0
+        return rate.buffer_rate_map(frames, fps, freq_min, freq_max, 4 if level is None else level, nfreq)
 
     calibrate = locate  # north_star names a calibrate(); the reference's calibration entry is locate()
 

@@ -110,6 +110,7 @@ extern "C" int rm_debug_set(rm_ctx *ctx, const char *key, long long value)
     const std::string k(key);
     if (k == "temporal_valu") d.temporal_valu = (int)value;
     else if (k == "temporal_wide") d.temporal_wide = (int)value;
+    else if (k == "rate_wide") d.rate_wide = (int)value;
     else if (k == "dc_lds_front_end") d.dc_lds_front_end = (int)value;
     else if (k == "bgr_unfused") d.bgr_unfused = (int)value;
     else if (k == "no_fused_bounds") d.no_fused_bounds = (int)value;

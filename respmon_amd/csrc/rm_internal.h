@@ -16,6 +16,7 @@
 //   rm_window.hip         rm_window_*: a ring of per-frame pyramid rows, relocated in place          (base.py:409-513 without the refill)
 //   rm_magnify.hip        rm_magnify, rm_magnify_bgr: frames + band-passed motion in one pass            (transforms.py:170, 181; rm_magnify.h)
 //   rm_stream.hip         rm_sosfilt, rm_stream_*: the causal band-pass in second-order sections with carried state, a live stream magnified chunk by chunk (rm_stream_kernels.h)
+//   rm_rate.hip           rm_spectral_peak, rm_rate_map: dominant in-band frequency per pixel column    (prototypes/temporal_analysis.py; rm_rate_kernels.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
 // A kernel is compiled in the ONE unit that launches it.  This header therefore includes no kernel header beyond what its own
 // declarations need (rm_kernels.h: the geometry structs, CollapseState, SumPlan; rm_flow_ws.h: rm_ctx embeds a FlowWorkspace) and what
@@ -93,6 +94,7 @@ struct CollapsePlan {
 struct DebugKnobs {
     int temporal_valu = 0;        // 1: the two-stage VALU temporal kernels instead of k_temporal_sym
     int temporal_wide = -1;       // 0 / 1: k_temporal_sym / k_temporal_sym_px whatever the level size (-1: by size)
+    int rate_wide = -1;           // 0 / 1: k_rate_peak / k_rate_peak_px whatever the level size (-1: by size)
     int bgr_unfused = 0;          // 1: RM_BGR8 buffers are converted to gray as a whole before the chain (the path of shapes the fused kernel does not take)
     int dc_lds_front_end = 0;     // 1: narrow frame buffers through the LDS front end of k_down_chain instead of rm_down_chain_u8.h
     int no_fused_bounds = 0;      // 1: k_small_collapse + k_frame_bounds instead of k_small_collapse_bounds
@@ -192,6 +194,8 @@ struct rm_ctx {
     int label_unl_n = 0, label_streak = 0;
     // cached temporal operator
     int op_T = 0, op_nk = 0; double op_fps = 0, op_fmin = 0, op_fmax = 0;
+    // cached spectral operator of the rate map (rm_rate.hip rate_operator; workspace buffer "rate_Af")
+    int rate_T = 0, rate_F = 0; double rate_fps = 0, rate_fmin = 0, rate_fmax = 0;
     bool state_fresh = false;   // d_state was reset by the last kernel of front_pyramid and nothing has reduced into it since
     int op_mfma = 0;        // > 0: the cached operator also exists in the fragment-major form of k_temporal_mfma, with this many 16-row tiles
     FlowWorkspace flow;
@@ -307,6 +311,10 @@ struct TemporalOp { const double *R = nullptr, *C = nullptr, *Rf = nullptr, *Cf 
 int get_operator(rm_ctx *ctx, int T, double fps, double fmin, double fmax, TemporalOp *op, hipStream_t s);
 int launch_temporal(rm_ctx *ctx, const double *x, int T, size_t NP, const TemporalOp &op, double amp, double *out, hipStream_t s,
                     rm::CollapseState *st_init = nullptr, bool full = false, int head = 0);   // head > 0: x is a ring of T rows, oldest frame in row `head`
+
+// ---- rm_rate.hip: the rate map of x[T, NP] (head > 0: a ring of T rows, oldest frame in row `head`); validates the band, nfreq and the outputs
+int rate_peak(rm_ctx *ctx, const double *x, int T, size_t NP, int head, double fps, double fmin, double fmax, int F, double *freq, double *power,
+              double *total, int32_t *index, hipStream_t s, const char *who);
 
 // ---- rm_down.hip: frames[T,H,W] -> G_S[T,h_S,w_S] in one launch
 int launch_down_chain(rm_ctx *ctx, const void *frames, int dtype, int T, const std::vector<int> &h, const std::vector<int> &w, int S,

@@ -6,6 +6,7 @@
 //   rm_temporal_kernels.h  temporal band-pass, lfilter                          rm_temporal.hip
 //   rm_small_kernels.h     small pyramid in LDS, tile bounds, filter-first      rm_front.hip, rm_collapse_eval.hip
 //   rm_select_kernels.h    selection, evaluation, min / max, masked sum         rm_collapse_eval.hip, rm_collapse_sum.hip, rm_calibrate.hip
+//   rm_rate_kernels.h      spectral peak per pixel column (rate map)            rm_rate.hip
 //   rm_heat_kernels.h      heatmap -> uint8 image, sparse heatmap packets       rm_roi.hip, rm_calibrate.hip
 //   rm_roi_kernels.h       dtype conversions, time average, ROI mean / crop     rm_ctx.hip, rm_temporal.hip, rm_motion.hip
 //

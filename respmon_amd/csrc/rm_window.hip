@@ -151,6 +151,22 @@ extern "C" int rm_window_locate_multi(rm_ctx *ctx, rm_window *w, double fps, dou
                                 n_out, stream, "rm_window_locate_multi");
 }
 
+// the rate map of the frames held (rm_rate.hip rate_peak), read from the ring in place: possible where a row IS G_skip of its frame
+extern "C" int rm_window_rate_map(rm_ctx *ctx, rm_window *w, double fps, double fmin, double fmax, int nfreq, double *freq, double *power,
+                                  double *total, int32_t *index, void *stream)
+{
+    if (!ctx || !w) return fail(RM_E_BADARG, "rm_window_rate_map: bad argument");
+    if (ctx->device != w->device) return fail(RM_E_BADARG, "rm_window_rate_map: the window belongs to device %d", w->device);
+    if (w->count < 2) return fail(RM_E_BADARG, "rm_window_rate_map: the window holds %d frame(s), a rate needs two", w->count);
+    if (!w->NP || !(w->pg.filter_first || w->pg.ff_levels))
+        return fail(RM_E_UNSUPPORTED, "rm_window_rate_map: the rows of this window are not the Gaussian level %d (Laplacian levels: flags, or its geometry)",
+                    w->skip);
+    HIP_TRY(hipSetDevice(ctx->device));
+    RM_TRY(ctx_stream_ok(ctx, stream, __func__));
+    return rate_peak(ctx, w->ring, w->count, w->NP, w->head, fps, fmin, fmax, nfreq, freq, power, total, index, (hipStream_t)stream,
+                     "rm_window_rate_map");
+}
+
 extern "C" int rm_debug_window_rows(rm_ctx *ctx, const rm_window *w, int row0, int nrows, double *out_host, void *stream)
 {
     if (!ctx || !w || !out_host || row0 < 0 || nrows < 0 || row0 + nrows > w->T) return fail(RM_E_BADARG, "rm_debug_window_rows: bad argument");

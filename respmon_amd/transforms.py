@@ -1,5 +1,6 @@
 """Device-backed counterparts of the reference's transforms.py hot-path functions (same names,
 argument meaning and return conventions).  numpy in -> numpy out; CUDA tensor in -> tensor out."""
+import collections
 import ctypes
 import logging
 
@@ -73,6 +74,37 @@ def temporal_bandpass_filter_fft(data, fps, freq_min=0.833, freq_max=1, axis=0,
     if verbose:
         print('{0}{1},{2}'.format(debug, float(out.min()), float(out.max())))
     return device.like_input(out, data)
+
+
+def spectral_operator(T, fps, freq_min, freq_max, nfreq):
+    """(A, freqs): the [2 nfreq, T] operator of spectral_peak -- row 2j / 2j+1 the Blackman-Harris windowed cosine / minus sine of
+    freqs[j] with the mean removal folded in -- and its frequency grid (rm_spectral_operator).  Host only; needs no GPU."""
+    from . import rate
+    return rate.spectral_operator_host(T, fps, freq_min, freq_max, nfreq)
+
+
+SpectralPeak = collections.namedtuple("SpectralPeak", "freq power total index")
+
+
+def spectral_peak(data, fps, freq_min=0.1, freq_max=1.0, nfreq=64):
+    """The frequency estimate of the reference's prototypes/temporal_analysis.py (Blackman-Harris window, spectrum of sig - sig.mean(),
+    argmax, parabolic(log .)) for every column of `data` [T, ...] at once, on a grid of `nfreq` frequencies from freq_min to freq_max
+    instead of the FFT bins (rm_spectral_peak; definition in include/respmon_hip.h).  Returns the named tuple (freq, power, total,
+    index) shaped data.shape[1:]: the refined peak frequency in Hz (NaN for a column that never changes), the power at the peak's grid
+    point, the power summed over the grid, and the grid point (-1 for such a column).  numpy in -> numpy out; device tensor in ->
+    device tensors out."""
+    t = device.require_gpu()
+    lib = _capi.load()
+    x = device.to_device(data, t.float64)
+    T = x.shape[0]
+    shape = tuple(x.shape[1:])
+    freq = t.empty(shape, dtype=t.float64, device=x.device)
+    power, total = t.empty_like(freq), t.empty_like(freq)
+    index = t.empty(shape, dtype=t.int32, device=x.device)
+    _capi.check(lib, lib.rm_spectral_peak(device.ctx(), device.ptr(x), T, freq.numel(), float(fps), float(freq_min), float(freq_max), int(nfreq),
+                                          device.ptr(freq), device.ptr(power), device.ptr(total), device.ptr(index), device.stream_ptr()),
+                "rm_spectral_peak")
+    return SpectralPeak(*(device.like_input(v, data) for v in (freq, power, total, index)))
 
 
 def butter_bandpass(_lowcut, _highcut, _fs, order=5):

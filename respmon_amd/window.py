@@ -21,6 +21,7 @@ class SlidingCalibration:
         t = device.require_gpu()
         self.lib = _capi.load()
         self.T, self.H, self.W = int(T), int(H), int(W)
+        self.skip_levels_at_top = int(skip_levels_at_top)
         self.device_index = t.cuda.current_device() if device_index is None else int(device_index)
         self.flags = int(flags) | (_capi.RM_FLAG_CONTOUR_CLIP_FRAME if RespiratoryMonitor.opencv_contours_clip_frame else 0) | \
             (_capi.RM_FLAG_FILTER_LAPLACIANS if RespiratoryMonitor.reference_operation_order else 0)
@@ -113,3 +114,11 @@ class SlidingCalibration:
                                                               ctypes.c_void_p(xywh.ctypes.data), None, ctypes.byref(n), self._stream()),
                     "rm_window_locate_multi")
         return [tuple(int(v) for v in xywh[i]) for i in range(n.value)]
+
+    # ------------------------------------------------------------------ rate out
+    def rate_map(self, fps, freq_min=0.1, freq_max=1.0, nfreq=64):
+        """rate.RateMap of the frames held (at least two), at pyramid level skip_levels_at_top: per pixel the dominant frequency in the
+        band and its share of the band's power, read from the ring in place (rm_window_rate_map).  Needs the default operation order
+        (the ring rows are the Gaussian level then)."""
+        from . import rate
+        return rate.window_rate_map(self, fps, freq_min, freq_max, nfreq)
