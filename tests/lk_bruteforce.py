@@ -1,7 +1,9 @@
 """TEST INFRASTRUCTURE: a plain float64 pyramidal Lucas-Kanade tracker, written independently of OpenCV's fixed-point one
 (no W_BITS weights, no DESCALE, no Scharr kernels, no early-exit rules): bilinear sampling with scipy's map_coordinates,
 central-difference gradients, Gauss-Newton on the 15 x 15 window, coarse to fine.  It bounds the error of the restated /
-HIP calcOpticalFlowPyrLK without a cv2 binary (Next 6b): on a smooth texture the two must agree to ~1e-3 px."""
+HIP calcOpticalFlowPyrLK without a cv2 binary (Next 6b): on a smooth texture the two must agree to ~1e-3 px.
+The sharper check is tests/tracker_reference.py: the tracker's own functional in real arithmetic, a tolerance derived per point, every
+window shape, the borders and the status byte; the 1e-2 / 3e-3 px held here were observed, not derived, and stay as they are."""
 import numpy as np
 import scipy.ndimage as ndi
 
