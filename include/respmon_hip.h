@@ -49,6 +49,20 @@ extern "C" {
  * base.py:230-231 (cv2.cvtColor(BGR2GRAY), then uint8_to_float) as they read the buffer: results are bit-identical to the same call on
  * the RM_U8 buffer that rm_bgr_to_gray makes of it.  Every other entry point takes gray frames and answers RM_E_BADARG. */
 #define RM_BGR8 4
+/* gray uint16: one 16-bit plane per frame, as infrared, thermal and depth cameras deliver it (Y16, or Y10 / Y12 / Y14 in 16-bit words).
+ * The kernels apply  uint16_to_float(k) = (double)k * (1./65535)  -- ONE float64 multiplication by the rounded constant, the shape of
+ * uint8_to_float -- as they read the buffer.  Every entry point that takes a gray dtype takes it, and returns bit for bit what the
+ * same call returns on the RM_F64 buffer that holds k * (1./65535) (the contract RM_F16 / RM_F32 have: "widened exactly").
+ *   - The low byte matters: 65 534 of the 65 536 values k * (1./65535) are not representable in float32, so nothing on this path
+ *     converts through a float or a half.
+ *   - Left-shifted samples: a 10 / 12 / 14-bit camera may store its samples shifted left by n bits or not.  Scaling every input by
+ *     2^n scales every float64 on the path exactly: the heat map comes out scaled by 2^n bit for bit, and the ROI, the normalised
+ *     uint8 heat map and the peaks of the mean signal are identical.  There is no white-level argument.  The optical-flow path alone
+ *     cares: rm_roi_to_uint8 makes trunc(x * 255) of a frame, so flow wants white at 65535 (shift such samples up first).
+ *   - (257 k) * (1./65535) is NOT k * (1./255) for 24 of the 256 k: an 8-bit stream widened to 16 bits does not reproduce the RM_U8
+ *     results bit for bit (the ROI normally agrees, the heat map does not).
+ * (The codes 5 and 7 stay unassigned.) */
+#define RM_U16 6
 
 /* rm_calibrate flags */
 #define RM_FLAG_NO_PRUNE 1u      /* evaluate every (tile, frame) of the collapse passes (A/B + verification) */
@@ -87,6 +101,10 @@ int rm_profile_read(rm_ctx *ctx, double *ms_host, int *n_host);
 /* ---- dtype helpers: transforms.py:20-23 uint8_to_float, transforms.py:26-29 float_to_uint8 */
 int rm_uint8_to_float(rm_ctx *ctx, const uint8_t *src_dev, double *dst_dev, size_t n, void *stream);
 int rm_float_to_uint8(rm_ctx *ctx, const double *src_dev, uint8_t *dst_dev, size_t n, void *stream);
+/* ... and the 16-bit pair (RM_U16 above): dst = (double)k * (1./65535);  dst = the low 16 bits of the C truncation of v * 65535,
+ * NaN and products outside int32 -> 0 (the rule of rm_float_to_uint8 with 65535 for 255) */
+int rm_uint16_to_float(rm_ctx *ctx, const uint16_t *src_dev, double *dst_dev, size_t n, void *stream);
+int rm_float_to_uint16(rm_ctx *ctx, const double *src_dev, uint16_t *dst_dev, size_t n, void *stream);
 
 /* ---- pyramid.py building blocks (materialising forms, API parity + tests) ------------- */
 /* cv2.pyrDown on every frame of src[T,h,w] -> dst[T,(h+1)/2,(w+1)/2] float64.  pyramid.py:14 */
@@ -168,7 +186,9 @@ int rm_eulerian_magnification_bandpass(rm_ctx *ctx, const void *frames_dev, int 
  * out_dev[T,H,W] of out_dtype:  RM_F64: m;  RM_F32: (float)m, round to nearest;  RM_U8: m clamped to [0, 1], then
  * rm_float_to_uint8's rule (transforms.py:26-29: the C truncation of m * 255; NaN -> 0).  The clamp is this library's: the
  * reference has no writer for this video, and without it a pixel pushed outside [0, 1] would wrap around modulo 256.
- * skip_levels_at_top >= pyramid_levels - 1 (nothing is filtered): raw is zero and the output is f converted.
+ * RM_U16: the same clamp, then rm_float_to_uint16's rule (the C truncation of m * 65535).
+ * skip_levels_at_top >= pyramid_levels - 1 (nothing is filtered): raw is zero and the output is f converted (an RM_U16 buffer
+ * magnified to RM_U16 comes back as u16(k * (1./65535) * 65535) per level: the rule, not an identity copy).
  * RM_E_BADARG: any other out_dtype, out_dev overlapping the frame buffer, NULL pointers, T < 1;  RM_E_UNSUPPORTED: T > 4096 as
  * in rm_calibrate.  Asynchronous on `stream`. */
 int rm_magnify(rm_ctx *ctx, const void *frames_dev, int dtype, int T, int H, int W,

@@ -20,6 +20,7 @@ RM_LOCATE_TICKETS = 2
 RM_MAX_ROIS = 64
 RM_U8, RM_F16, RM_F32, RM_F64 = 0, 1, 2, 3
 RM_BGR8 = 4   # frame buffers only: [T,H,W,3] uint8 in cv2.VideoCapture's channel order (include/respmon_hip.h)
+RM_U16 = 6    # gray uint16 (Y16): the kernels apply k * (1./65535) (include/respmon_hip.h)
 RM_FLAG_NO_PRUNE = 1
 RM_FLAG_UNFUSED_DOWN = 2
 RM_FLAG_TINY_STORE = 4
@@ -57,6 +58,8 @@ SIGNATURES = {
     "rm_debug_chain_stitch": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "rm_uint8_to_float": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "rm_float_to_uint8": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "rm_uint16_to_float": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "rm_float_to_uint16": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "rm_pyr_down": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "rm_pyr_up": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
     "rm_create_laplacian_video_pyramid": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _c.POINTER(_vp), _vp]),

@@ -149,25 +149,38 @@ class _Backend:
         self.last_bgr = src     # the frame as captured, on the device: what a 'bgr8' calibration buffer stores (store_frame's `bgr`)
         return gray
 
+    def gray16(self, y16_host):
+        """a 2-D uint16 frame of the capture (Y16) as it is, on the device: no cvtColor, no narrowing"""
+        return self.t.from_numpy(np.ascontiguousarray(y16_host)).cuda()
+
     def store_frame(self, buf, idx, gray_u8, bgr=None):
         """calibration_buffer[idx][:] = uint8_to_float(gray) (base.py:231, 431).
+        A uint16 frame (Y16) goes into a 'uint16' buffer as it is, or through rm_uint16_to_float (k * (1./65535)) into a float buffer:
+        float64 exact, a narrower one rounded once.  An 8-bit buffer has no place for it, and a 'uint16' buffer none for an 8-bit frame
+        (the two scales differ: include/respmon_hip.h RM_U16): TypeError.
         A 'bgr8' buffer ([T,H,W,3] uint8) stores the frame AS CAPTURED: pass the device BGR tensor the gray frame came from as
         `bgr` (RespiratoryMonitor.step does: the tensor next_frame() kept).  Without it -- a gray frame from another source:
         replayed, processed, another backend's ingest -- the gray value goes into all three planes, which base.py:230's
         conversion maps back to exactly that gray value (Y(x, x, x) == x), so the calibration reads the same frame either way."""
         t = self.t
+        frame16, buf16 = gray_u8.dtype == t.uint16, buf.dtype == t.uint16
+        if (frame16 and buf.dtype == t.uint8) or (buf16 and not frame16):
+            raise TypeError("a %s frame does not go into a %s calibration buffer (uint16 frames: buffer_dtype 'uint16' or a float dtype; "
+                            "uint8 / BGR frames: any other buffer_dtype)"
+                            % (str(gray_u8.dtype).replace("torch.", ""), "bgr8" if buf.dim() == 4 else str(buf.dtype).replace("torch.", "")))
         if buf.dim() == 4:
             # buffer_dtype 'bgr8': rm_locate applies base.py:230-231 when it reads the buffer (RM_BGR8)
             if bgr is not None:
                 buf[idx].copy_(bgr)
             else:
                 buf[idx].copy_(gray_u8.unsqueeze(-1).expand(-1, -1, 3))
-        elif buf.dtype == t.uint8:
+        elif buf.dtype == t.uint8 or buf16:
             buf[idx].copy_(gray_u8)
         else:
             dst64 = buf[idx] if buf.dtype == t.float64 else t.empty(gray_u8.shape, dtype=t.float64, device=gray_u8.device)
-            _capi.check(self.lib, self.lib.rm_uint8_to_float(device.ctx(), device.ptr(gray_u8), device.ptr(dst64),
-                                                             gray_u8.numel(), device.stream_ptr()), "rm_uint8_to_float")
+            fn = "rm_uint16_to_float" if frame16 else "rm_uint8_to_float"
+            _capi.check(self.lib, getattr(self.lib, fn)(device.ctx(), device.ptr(gray_u8), device.ptr(dst64),
+                                                        gray_u8.numel(), device.stream_ptr()), fn)
             if buf.dtype != t.float64:   # narrower float buffer: round the float64 value to the storage dtype
                 buf[idx].copy_(dst64)
 
@@ -379,7 +392,11 @@ class RespiratoryMonitor(BreathSignal):
                  motion_extraction_method='average', buffer_dtype='float64', run_on_init=True, backend=None, relocate_every=0):
         """Arguments as reference base.py:24-34, plus (not in the reference):
         buffer_dtype -- element type of the calibration buffer in HBM: 'float64' (the reference's, base.py:119), 'float32',
-            'float16', 'uint8' (the gray frame as ingested; uint8_to_float happens where the buffer is read) or 'bgr8' (a
+            'float16', 'uint8' (the gray frame as ingested; uint8_to_float happens where the buffer is read), 'uint16' (the same for
+            the 2-D uint16 frames of a Y16 capture -- infrared, thermal, depth: k * (1./65535) where the buffer is read; such frames
+            also go into the float dtypes, and neither into nor out of the 8-bit ones: TypeError.  White is 65535: the 'flow' method
+            crops trunc(x * 255) of a frame, so right-aligned 10 / 12 / 14-bit samples should be shifted up first; 'average' and the
+            calibration do not care) or 'bgr8' (a
             [T,H,W,3] uint8 buffer of the frames AS CAPTURED: cvtColor + uint8_to_float happen where the buffer is read; next_frame()
             keeps the device copy of the captured frame for step(), a frame from anywhere else is stored as its gray value in
             three planes -- the same calibration either way);
@@ -406,7 +423,7 @@ class RespiratoryMonitor(BreathSignal):
             "error_reset_delay must be a positive int or float"
         assert isinstance(save_all_data, bool), "save_all_data should be bool"
         assert motion_extraction_method in ("average", "flow"), "motion_extraction_method must be 'average' or 'flow'"
-        assert buffer_dtype in ("float64", "float32", "float16", "uint8", "bgr8")
+        assert buffer_dtype in ("float64", "float32", "float16", "uint8", "uint16", "bgr8")
         assert isinstance(relocate_every, int) and relocate_every >= 0, "relocate_every must be a non-negative int"
 
         self.benchmarker = Benchmarker()
@@ -499,18 +516,21 @@ class RespiratoryMonitor(BreathSignal):
             t = device.require_gpu()
             if self.buffer_dtype == "bgr8":    # north_star's [T,H,W,C] frame buffer: frames as captured, 3 bytes per pixel
                 return t.zeros((self.calibration_buffer_target_length, self.height, self.width, 3), dtype=t.uint8, device="cuda")
+            shape = (self.calibration_buffer_target_length, self.height, self.width)
+            if self.buffer_dtype == "uint16":  # (zeroed through its bits: torch fills few unsigned types wider than a byte on the device)
+                return t.zeros(shape, dtype=t.int16, device="cuda").view(t.uint16)
             dt = {"float64": t.float64, "float32": t.float32, "float16": t.float16, "uint8": t.uint8}[self.buffer_dtype]
-            return t.zeros((self.calibration_buffer_target_length, self.height, self.width), dtype=dt, device="cuda")
+            return t.zeros(shape, dtype=dt, device="cuda")
         return self._backend.alloc_buffer(self.calibration_buffer_target_length, self.height, self.width, self.buffer_dtype)
 
     @property
     def current_frame(self):
-        """float64 [H,W] host copy of the current frame (uint8_to_float(gray), base.py:231)."""
+        """float64 [H,W] host copy of the current frame (uint8_to_float(gray), base.py:231; a uint16 frame: k * (1./65535))."""
         if self._frame_u8 is None:
             return None
         g = self._frame_u8
         g = g.cpu().numpy() if hasattr(g, "cpu") else np.asarray(g)
-        return g * (1. / 255)
+        return g * (1. / 65535) if g.dtype == np.uint16 else g * (1. / 255)
 
     # ------------------------------------------------------------------ reference methods
     def skip_calibration(self, x, y, w, h):
@@ -520,8 +540,13 @@ class RespiratoryMonitor(BreathSignal):
         self.state = 'measure'
 
     def next_frame(self):
-        """base.py:227-233: read -> BGR2GRAY -> (uint8_to_float is applied by the consumers); False at end."""
+        """base.py:227-233: read -> BGR2GRAY -> (uint8_to_float is applied by the consumers); False at end.
+        A 2-D uint16 frame (a Y16 capture with CAP_PROP_CONVERT_RGB off) is gray already: it stays uint16, on the device."""
         ret, frame = self.cap.read()
+        if ret and getattr(frame, "ndim", 0) == 2 and frame.dtype == np.uint16:
+            self._frame_u8, self._frame_bgr = self._backend.gray16(frame), None
+            self.frames_consumed += 1
+            return self._frame_u8
         if ret:
             self._frame_u8 = self._backend.bgr_to_gray(frame)
             # a 'bgr8' calibration buffer stores the frame as captured: keep the device copy the backend made of it for step()
@@ -745,8 +770,8 @@ class RespiratoryMonitor(BreathSignal):
         """The current calibration buffer with its breathing motion amplified -- what locate() looks at, frame by frame: the frames plus
         the band-passed signal of locate()'s defaults (amplification 500, pyramid_levels 9, skip_levels_at_top 4) at the monitor's fps,
         freq_min and freq_max (transforms.eulerian_magnification_video).  A device tensor [T,H,W]; `out_dtype` None: uint8 for a uint8 or
-        'bgr8' buffer, float64 otherwise.  `color=True` (buffer_dtype 'bgr8' only): the frames as captured with that motion laid over
-        them, [T,H,W,3] uint8 BGR."""
+        'bgr8' buffer, uint16 for a uint16 one, float64 otherwise.  `color=True` (buffer_dtype 'bgr8' only): the frames as captured with
+        that motion laid over them, [T,H,W,3] uint8 BGR."""
         from .transforms import eulerian_magnification_video
         if color and not device.is_bgr_buffer(self.calibration_buffer):
             raise ValueError("magnified_calibration_video(color=True) needs buffer_dtype='bgr8'; this monitor's buffer_dtype is %r"
@@ -789,12 +814,12 @@ class RespiratoryMonitor(BreathSignal):
         """`frame` and up to measure_clip_length - 1 further captured frames as one clip; False when the capture ended."""
         K = int(self.measure_clip_length)
         buf = getattr(self, "_clip_buf", None)
-        if buf is None or len(buf) != K or tuple(buf.shape[1:]) != tuple(frame.shape):
+        if buf is None or len(buf) != K or tuple(buf.shape[1:]) != tuple(frame.shape) or buf.dtype != frame.dtype:
             if isinstance(frame, np.ndarray):
-                buf = np.empty((K,) + tuple(frame.shape), dtype=np.uint8)
+                buf = np.empty((K,) + tuple(frame.shape), dtype=frame.dtype)
             else:
                 t = device.torch()
-                buf = t.empty((K,) + tuple(frame.shape), dtype=t.uint8, device=frame.device)
+                buf = t.empty((K,) + tuple(frame.shape), dtype=frame.dtype, device=frame.device)
             self._clip_buf = buf
         buf[0] = frame
         n, open_ = 1, True

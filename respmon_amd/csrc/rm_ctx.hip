@@ -258,6 +258,24 @@ extern "C" int rm_float_to_uint8(rm_ctx *ctx, const double *src, uint8_t *dst, s
     return RM_OK;
 }
 
+extern "C" int rm_uint16_to_float(rm_ctx *ctx, const uint16_t *src, double *dst, size_t n, void *stream)
+{
+    if (!ctx || !src || !dst) return fail(RM_E_BADARG, "rm_uint16_to_float: NULL argument");
+    if (n == 0) return RM_OK;
+    hipLaunchKernelGGL(k_u16_to_f64<>, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, n);
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
+extern "C" int rm_float_to_uint16(rm_ctx *ctx, const double *src, uint16_t *dst, size_t n, void *stream)
+{
+    if (!ctx || !src || !dst) return fail(RM_E_BADARG, "rm_float_to_uint16: NULL argument");
+    if (n == 0) return RM_OK;
+    hipLaunchKernelGGL(k_f64_to_u16<>, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, n);
+    LAUNCH_CHECK();
+    return RM_OK;
+}
+
 int launch_bgr_to_gray(const uint8_t *bgr, size_t npix, uint8_t *gray, hipStream_t s)
 {
     if (npix == 0) return RM_OK;

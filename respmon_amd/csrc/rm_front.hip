@@ -73,7 +73,7 @@ int front_pyramid(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int 
     if (pg.filter_first || pg.ff_levels) {
         // filter-first form: the array the stages exchange is G_S itself; the small pyramid is built after the temporal filter
         PhaseTimer pt(ctx, 0, s);
-        RM_TRY(launch_down_chain(ctx, frames, dtype, T, h, w, S, lap, s, (flags & RM_FLAG_TINY_STRIPS) != 0));
+        RM_TRY(launch_frames_down(ctx, frames, dtype, T, h, w, S, lap, s, (flags & RM_FLAG_TINY_STRIPS) != 0));
         host_mark(ctx, 1);
         ctx->state_fresh = false;
         return RM_OK;
@@ -84,7 +84,7 @@ int front_pyramid(rm_ctx *ctx, const void *frames, int dtype, int T, int H, int 
         RM_TRY(ws(ctx, "g" + std::to_string(S), (size_t)T * h[S] * w[S], &dst));
         {
             PhaseTimer pt(ctx, 0, s);
-            RM_TRY(launch_down_chain(ctx, frames, dtype, T, h, w, S, dst, s, (flags & RM_FLAG_TINY_STRIPS) != 0));
+            RM_TRY(launch_frames_down(ctx, frames, dtype, T, h, w, S, dst, s, (flags & RM_FLAG_TINY_STRIPS) != 0));
         }
         g[S] = dst; cur = dst; cur_dtype = RM_F64;
         first = S + 1;

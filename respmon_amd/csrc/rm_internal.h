@@ -279,12 +279,13 @@ static inline unsigned nblk(size_t n, unsigned per, unsigned cap = 8192)
     if (b < 1) b = 1;
     return (unsigned)(b > cap ? cap : b);
 }
-static inline bool valid_dtype(int d) { return d == RM_U8 || d == RM_F16 || d == RM_F32 || d == RM_F64; }
-// f(T()) with T the element type of a frame dtype (valid_dtype): the one four-way switch behind the kernels templated on it
+static inline bool valid_dtype(int d) { return d == RM_U8 || d == RM_F16 || d == RM_F32 || d == RM_F64 || d == RM_U16; }
+// f(T()) with T the element type of a frame dtype (valid_dtype): the one five-way switch behind the kernels templated on it
 template <typename F> static inline void dispatch_dtype(int dtype, F &&f)
 {
     switch (dtype) {
     case RM_U8: f(uint8_t()); break;
+    case RM_U16: f(uint16_t()); break;
     case RM_F16: f(__half()); break;
     case RM_F32: f(float()); break;
     default: f(double()); break;
@@ -292,8 +293,8 @@ template <typename F> static inline void dispatch_dtype(int dtype, F &&f)
 }
 // frame BUFFERS of the calibration entry points may also be RM_BGR8 ([T,H,W,3] uint8: base.py:230's cvtColor happens on the device)
 static inline bool valid_buffer_dtype(int d) { return valid_dtype(d) || d == RM_BGR8; }
-static inline int dtype_vec(int dtype) { return dtype == RM_F64 ? 2 : dtype == RM_F32 ? 4 : dtype == RM_F16 ? 8 : 16; }   // pixels per 16-byte aligned lane-load unit
-static inline size_t dtype_size(int dtype) { return dtype == RM_F64 ? 8 : dtype == RM_F32 ? 4 : dtype == RM_F16 ? 2 : dtype == RM_BGR8 ? 3 : 1; }
+static inline int dtype_vec(int dtype) { return dtype == RM_F64 ? 2 : dtype == RM_F32 ? 4 : (dtype == RM_F16 || dtype == RM_U16) ? 8 : 16; }   // pixels per 16-byte aligned lane-load unit
+static inline size_t dtype_size(int dtype) { return dtype == RM_F64 ? 8 : dtype == RM_F32 ? 4 : (dtype == RM_F16 || dtype == RM_U16) ? 2 : dtype == RM_BGR8 ? 3 : 1; }
 
 // ---- rm_ctx.hip
 int launch_bgr_to_gray(const uint8_t *bgr, size_t npix, uint8_t *gray, hipStream_t s);
@@ -319,6 +320,17 @@ int rate_peak(rm_ctx *ctx, const double *x, int T, size_t NP, int head, double f
 // ---- rm_down.hip: frames[T,H,W] -> G_S[T,h_S,w_S] in one launch
 int launch_down_chain(rm_ctx *ctx, const void *frames, int dtype, int T, const std::vector<int> &h, const std::vector<int> &w, int S,
                       double *out, hipStream_t s, bool tiny);
+// ---- rm_down_u16.hip: the same for an RM_U16 buffer.  A unit and a header (rm_down_u16.h) of their own: the sources above are hashed into
+// rm_debug_kernel_source_stamp, and the kernels the committed PMC figures were measured on do not change when a dtype is added
+int launch_down_chain_u16(rm_ctx *ctx, const void *frames, int T, const std::vector<int> &h, const std::vector<int> &w, int S, double *out,
+                          hipStream_t s, bool tiny);
+// ... and the one the entry points call: any frame-buffer dtype
+static inline int launch_frames_down(rm_ctx *ctx, const void *frames, int dtype, int T, const std::vector<int> &h, const std::vector<int> &w, int S,
+                                     double *out, hipStream_t s, bool tiny)
+{
+    if (dtype == RM_U16) return launch_down_chain_u16(ctx, frames, T, h, w, S, out, s, tiny);
+    return launch_down_chain(ctx, frames, dtype, T, h, w, S, out, s, tiny);
+}
 
 // ---- rm_front.hip
 struct SmallLevels {

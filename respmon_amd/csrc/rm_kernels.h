@@ -140,6 +140,10 @@ __host__ __device__ __forceinline__ size_t slot_index(int u, int tile, int Th) {
 
 // widening loads; uint8 applies uint8_to_float's  k * (1./255)  (transforms.py:20-23)
 __device__ __forceinline__ double load_px(const uint8_t *p, size_t i) { return (double)p[i] * (1.0 / 255); }
+// uint16 (RM_U16): uint16_to_float's  k * (1./65535), one float64 multiplication.  Never through a float: 65 534 of the 65 536 values
+// are not float32 numbers
+__device__ __forceinline__ double u16_to_f64(unsigned k) { return (double)k * (1.0 / 65535); }
+__device__ __forceinline__ double load_px(const uint16_t *p, size_t i) { return u16_to_f64(p[i]); }
 __device__ __forceinline__ double load_px(const __half *p, size_t i) { return (double)__half2float(p[i]); }
 __device__ __forceinline__ double load_px(const float *p, size_t i) { return (double)p[i]; }
 __device__ __forceinline__ double load_px(const double *p, size_t i) { return p[i]; }
@@ -162,6 +166,12 @@ __device__ __forceinline__ uint8_t f64_to_u8_trunc(double v255)
 {
     if (!(v255 == v255) || v255 >= 2147483648.0 || v255 <= -2147483649.0) return 0;
     return (uint8_t)((int)v255 & 255);
+}
+// float_to_uint16: the same rule on v * 65535, low 16 bits
+__device__ __forceinline__ uint16_t f64_to_u16_trunc(double v65535)
+{
+    if (!(v65535 == v65535) || v65535 >= 2147483648.0 || v65535 <= -2147483649.0) return 0;
+    return (uint16_t)((int)v65535 & 65535);
 }
 
 // Wave (64-lane) reductions; the result is valid in every lane.

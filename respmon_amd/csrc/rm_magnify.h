@@ -10,7 +10,7 @@
 // Output: RM_F64 m; RM_F32 (float)m, round to nearest; RM_U8 m clamped to [0, 1] and then rm_float_to_uint8's rule (transforms.py:26-29,
 // the C truncation of m * 255; NaN -> 0 as there).  THE CLAMP IS OURS: the reference has no writer for this video, and a magnified pixel
 // leaves [0, 1] wherever the amplified motion is larger than the head room of the frame -- without the clamp such a pixel would wrap
-// around modulo 256.
+// around modulo 256.  RM_U16: the same clamp, then rm_float_to_uint16's rule (the C truncation of m * 65535).
 //
 //   * k_magnify<S, Tin, Tout>: a wave owns a 64 x 16 tile and MAG_FC consecutive UNIQUE frames u (the band-passed signal is even in time,
 //     rm_kernels.h sym_frame: raw[T - u] is raw[u] again).  Per u it stages the tile's level-S footprint of C_S[u], evaluates raw with
@@ -53,6 +53,10 @@ template <> struct MagPx<uint8_t> {
     using E = uint8_t; static constexpr int C = 1;
     static __device__ __forceinline__ double widen(const E *e) { return (double)e[0] * (1.0 / 255); }
 };
+template <> struct MagPx<uint16_t> {   // RM_U16: uint16_to_float's k * (1./65535)
+    using E = uint16_t; static constexpr int C = 1;
+    static __device__ __forceinline__ double widen(const E *e) { return u16_to_f64(e[0]); }
+};
 template <> struct MagPx<__half> {
     using E = uint16_t; static constexpr int C = 1;
     static __device__ __forceinline__ double widen(const E *e)
@@ -86,6 +90,11 @@ template <> __device__ __forceinline__ uint8_t mag_out<uint8_t>(double m)
 {
     const double c = m < 0.0 ? 0.0 : (m > 1.0 ? 1.0 : m);   // (NaN passes through: f64_to_u8_trunc maps it to 0)
     return f64_to_u8_trunc(c * 255);
+}
+template <> __device__ __forceinline__ uint16_t mag_out<uint16_t>(double m)   // the same clamp, for the same reason, then float_to_uint16's rule
+{
+    const double c = m < 0.0 ? 0.0 : (m > 1.0 ? 1.0 : m);
+    return f64_to_u16_trunc(c * 65535);
 }
 
 constexpr int MAG_FC = 8;                      // unique frames per work item

@@ -50,6 +50,7 @@ int launch_out(const MagCall &c, int out_dtype, const double *cS, const ChainGeo
 {
     switch (out_dtype) {
     case RM_U8: return launch_any<Tin, uint8_t, SYM>(c, cS, g, raw);
+    case RM_U16: return launch_any<Tin, uint16_t, SYM>(c, cS, g, raw);
     case RM_F32: return launch_any<Tin, float, SYM>(c, cS, g, raw);
     default: return launch_any<Tin, double, SYM>(c, cS, g, raw);
     }
@@ -60,6 +61,7 @@ int launch_in(const MagCall &c, int dtype, int out_dtype, const double *cS, cons
 {
     switch (dtype) {
     case RM_U8: return launch_out<uint8_t, SYM>(c, out_dtype, cS, g, raw);
+    case RM_U16: return launch_out<uint16_t, SYM>(c, out_dtype, cS, g, raw);
     case RM_F16: return launch_out<__half, SYM>(c, out_dtype, cS, g, raw);
     case RM_F32: return launch_out<float, SYM>(c, out_dtype, cS, g, raw);
     case RM_F64: return launch_out<double, SYM>(c, out_dtype, cS, g, raw);
@@ -123,8 +125,8 @@ extern "C" int rm_magnify(rm_ctx *ctx, const void *frames, int dtype, int T, int
 {
     if (!ctx || !frames || !out || T < 1 || H < 1 || W < 1 || levels < 1 || skip < 0 || !(fps > 0) || !valid_buffer_dtype(dtype))
         return fail(RM_E_BADARG, "rm_magnify: bad argument");
-    if (out_dtype != RM_U8 && out_dtype != RM_F32 && out_dtype != RM_F64)
-        return fail(RM_E_BADARG, "rm_magnify: out_dtype %d (RM_U8, RM_F32 or RM_F64)", out_dtype);
+    if (out_dtype != RM_U8 && out_dtype != RM_U16 && out_dtype != RM_F32 && out_dtype != RM_F64)
+        return fail(RM_E_BADARG, "rm_magnify: out_dtype %d (RM_U8, RM_U16, RM_F32 or RM_F64)", out_dtype);
     if (T > MAX_T) return fail(RM_E_UNSUPPORTED, "rm_magnify: T=%d > %d", T, MAX_T);
     const size_t n = (size_t)T * H * W;
     if (ranges_overlap(frames, n * dtype_size(dtype), out, n * dtype_size(out_dtype))) return fail(RM_E_BADARG, "rm_magnify: out_dev overlaps the frame buffer");

@@ -154,6 +154,6 @@ extern "C" int rm_rate_map(rm_ctx *ctx, const void *frames_dev, int dtype, int T
     const size_t NP = (size_t)h[level] * w[level];
     double *g = nullptr;
     RM_TRY(ws(ctx, "rate_g", (size_t)T * NP, &g));
-    RM_TRY(launch_down_chain(ctx, frames_dev, dtype, T, h, w, level, g, s, false));
+    RM_TRY(launch_frames_down(ctx, frames_dev, dtype, T, h, w, level, g, s, false));
     return rate_peak(ctx, g, T, NP, 0, fps, fmin, fmax, nfreq, freq_dev, power_dev, total_dev, index_dev, s, "rm_rate_map");
 }

@@ -32,6 +32,19 @@ RM_KERNEL __launch_bounds__(256) void k_f64_to_u8(const double *src, uint8_t *ds
         dst[i] = f64_to_u8_trunc(src[i] * 255);
 }
 
+// the 16-bit pair (RM_U16, include/respmon_hip.h): k * (1./65535), and the C truncation of v * 65535
+RM_KERNEL __launch_bounds__(256) void k_u16_to_f64(const uint16_t *src, double *dst, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        dst[i] = load_px(src, i);
+}
+
+RM_KERNEL __launch_bounds__(256) void k_f64_to_u16(const double *src, uint16_t *dst, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        dst[i] = f64_to_u16_trunc(src[i] * 65535);
+}
+
 // np.average(frame[y:y+h, x:x+w]) (base.py:357): numpy's pairwise order is not reproduced; any
 // float64 order is within ~1e-13 relative of it.  One block; wave partials summed in lane order.
 template <typename Tin>

@@ -147,8 +147,8 @@ static int stream_chunk(rm_ctx *ctx, rm_stream *st, const void *frames, int dtyp
 extern "C" int rm_stream_push(rm_ctx *ctx, rm_stream *st, const void *frames, int dtype, int n, void *out, int out_dtype, void *stream)
 {
     if (!ctx || !st || !frames || !out || n < 1 || !valid_buffer_dtype(dtype)) return fail(RM_E_BADARG, "rm_stream_push: bad argument");
-    if (out_dtype != RM_U8 && out_dtype != RM_F32 && out_dtype != RM_F64 && out_dtype != RM_BGR8)
-        return fail(RM_E_BADARG, "rm_stream_push: out_dtype %d (RM_U8, RM_F32, RM_F64 or RM_BGR8)", out_dtype);
+    if (out_dtype != RM_U8 && out_dtype != RM_U16 && out_dtype != RM_F32 && out_dtype != RM_F64 && out_dtype != RM_BGR8)
+        return fail(RM_E_BADARG, "rm_stream_push: out_dtype %d (RM_U8, RM_U16, RM_F32, RM_F64 or RM_BGR8)", out_dtype);
     if (out_dtype == RM_BGR8 && dtype != RM_BGR8) return fail(RM_E_BADARG, "rm_stream_push: RM_BGR8 output needs RM_BGR8 frames");
     if (ctx->device != st->device) return fail(RM_E_BADARG, "rm_stream_push: the stream belongs to device %d", st->device);
     const size_t npix = (size_t)st->H * st->W, in_fb = npix * dtype_size(dtype), out_fb = npix * dtype_size(out_dtype);

@@ -8,7 +8,7 @@ from . import _capi
 
 _CTX = {}
 
-_NP_CODES = {np.dtype(np.uint8): _capi.RM_U8, np.dtype(np.float16): _capi.RM_F16,
+_NP_CODES = {np.dtype(np.uint8): _capi.RM_U8, np.dtype(np.uint16): _capi.RM_U16, np.dtype(np.float16): _capi.RM_F16,
              np.dtype(np.float32): _capi.RM_F32, np.dtype(np.float64): _capi.RM_F64}
 
 
@@ -78,9 +78,9 @@ def stream_ptr():
 
 def dtype_code(tensor):
     t = torch()
-    table = {t.uint8: _capi.RM_U8, t.float16: _capi.RM_F16, t.float32: _capi.RM_F32, t.float64: _capi.RM_F64}
+    table = {t.uint8: _capi.RM_U8, t.uint16: _capi.RM_U16, t.float16: _capi.RM_F16, t.float32: _capi.RM_F32, t.float64: _capi.RM_F64}
     if tensor.dtype not in table:
-        raise TypeError("unsupported frame dtype %s (uint8, float16, float32, float64)" % tensor.dtype)
+        raise TypeError("unsupported frame dtype %s (uint8, uint16, float16, float32, float64)" % tensor.dtype)
     return table[tensor.dtype]
 
 

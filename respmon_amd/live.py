@@ -21,9 +21,9 @@ class LiveMagnifier:
     (scipy.signal.sosfilt_zi times the frame's pyramid) -- a band-pass has no DC gain, so the output starts at the frame itself
     instead of seconds of ringing from the step black -> first frame.  start='rest': scipy.signal.sosfilt's default.
 
-    push(frames): [n,H,W] or [H,W] of uint8 / float16 / float32 / float64, or [n,H,W,3] / [H,W,3] uint8 BGR; numpy in -> numpy out,
-    device tensor in -> device tensor out, of the same number of frames.  out_dtype 'uint8' | 'float32' | 'float64' (None: uint8 for
-    uint8 and BGR input, float64 otherwise, as eulerian_magnification_video); color=True: BGR frames in, BGR frames out, the same
+    push(frames): [n,H,W] or [H,W] of uint8 / uint16 / float16 / float32 / float64, or [n,H,W,3] / [H,W,3] uint8 BGR; numpy in -> numpy
+    out, device tensor in -> device tensor out, of the same number of frames.  out_dtype 'uint8' | 'uint16' | 'float32' | 'float64' (None:
+    uint8 for uint8 and BGR input, uint16 for uint16 input, float64 otherwise, as eulerian_magnification_video); color=True: BGR frames in, BGR frames out, the same
     motion on the three channels (rm_magnify_bgr's rule).  A change of fps or band needs a new object."""
 
     def __init__(self, H, W, fps, freq_min=0.1, freq_max=1.0, amplification=50, pyramid_levels=4, skip_levels_at_top=2, order=6,
@@ -37,8 +37,8 @@ class LiveMagnifier:
         self.H, self.W = int(H), int(W)
         self.color = bool(color)
         name = None if out_dtype is None else getattr(out_dtype, "__name__", str(out_dtype).replace("torch.", "").replace("numpy.", ""))
-        if name not in (None, "uint8", "float32", "float64"):
-            raise TypeError("out_dtype must be uint8, float32 or float64, got %r" % (out_dtype,))
+        if name not in (None, "uint8", "uint16", "float32", "float64"):
+            raise TypeError("out_dtype must be uint8, uint16, float32 or float64, got %r" % (out_dtype,))
         if self.color and name not in (None, "uint8"):
             raise TypeError("out_dtype must be None or uint8 with color=True, got %r" % (out_dtype,))
         self.out_name = name
@@ -106,8 +106,9 @@ class LiveMagnifier:
                 raise ValueError("color=True needs [n,H,W,3] uint8 BGR frames, got %s %s" % (tuple(x.shape), x.dtype))
             out, out_code = t.empty_like(x), _capi.RM_BGR8
         else:
-            name = self.out_name or ("uint8" if x.dtype == t.uint8 else "float64")
-            table = {"uint8": (t.uint8, _capi.RM_U8), "float32": (t.float32, _capi.RM_F32), "float64": (t.float64, _capi.RM_F64)}
+            name = self.out_name or ("uint8" if x.dtype == t.uint8 else "uint16" if x.dtype == t.uint16 else "float64")
+            table = {"uint8": (t.uint8, _capi.RM_U8), "uint16": (t.uint16, _capi.RM_U16), "float32": (t.float32, _capi.RM_F32),
+                     "float64": (t.float64, _capi.RM_F64)}
             out, out_code = t.empty((n, H, W), dtype=table[name][0], device=x.device), table[name][1]
         if n:
             _capi.check(self.lib, self.lib.rm_stream_push(self._ctx(), self._h, device.ptr(x), code, n, device.ptr(out), out_code,

@@ -61,7 +61,7 @@ def level_shape(H, W, level):
 
 
 def buffer_rate_map(frames, fps, freq_min=0.1, freq_max=1.0, level=4, nfreq=64):
-    """RateMap of a frame buffer ([T,H,W] of uint8 / float16 / float32 / float64, or [T,H,W,3] uint8 BGR; numpy or device tensor) at
+    """RateMap of a frame buffer ([T,H,W] of uint8 / uint16 / float16 / float32 / float64, or [T,H,W,3] uint8 BGR; numpy or device tensor) at
     Gaussian pyramid level `level` (1..5): one pass over the frames (rm_rate_map)."""
     device.require_gpu()
     lib = _capi.load()

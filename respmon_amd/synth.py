@@ -50,6 +50,19 @@ def synth_breathing(T, H, W, seed=1234, fps=10.0, breath_hz=0.4, amplitude=0.2, 
     return out
 
 
+def synth_breathing16(T, H, W, seed=1234, bits=16, **kw):
+    """uint16 [T,H,W] gray video as a 16-bit camera delivers it (Y16): synth_breathing(T, H, W, seed, **kw) in the upper byte and seeded
+    uniform noise in the lower one, so that every bit of a sample carries information.  `bits` < 16: the sample of a 10 / 12 / 14-bit
+    sensor stored right-aligned in its 16-bit word, i.e. the 16-bit sample shifted down by 16 - bits (shift it up again for the
+    left-aligned form: the calibration finds the same ROI either way, include/respmon_hip.h RM_U16)."""
+    if not 1 <= bits <= 16:
+        raise ValueError("bits must be 1..16, got %r" % (bits,))
+    hi = synth_breathing(T, H, W, seed=seed, **kw).astype(np.uint16)
+    rng = np.random.Generator(np.random.PCG64([seed, 16]))
+    lo = rng.integers(0, 256, size=(T, H, W), dtype=np.uint16)
+    return ((hi << 8) | lo) >> np.uint16(16 - bits)
+
+
 def synth_breathing_blocks(T, H, W, seed=1234, fps=10.0, breath_hz=0.4, amplitude=0.2, noise=0.02,
                            center=(0.6, 0.4), sigma=(0.10, 0.08), block=8, workers=None):
     """The same video model as synth_breathing for the large configurations (4K x 512 is 4.2 G samples): every `block`
@@ -184,7 +197,8 @@ def synth_texture(H, W, seed=4321, n_waves=12, n_spots=40):
 
 class FakeCapture:
     """Stands in for cv2.VideoCapture (reference base.py:48-51, 227-233).
-    frames: uint8 [T,H,W,3] BGR (or [T,H,W] gray, returned as 3 equal channels)."""
+    frames: uint8 [T,H,W,3] BGR (or [T,H,W] gray, returned as 3 equal channels); uint16 [T,H,W] frames are returned as they are, 2-D,
+    as a Y16 capture with CAP_PROP_CONVERT_RGB off delivers them."""
 
     def __init__(self, frames, fps=10):
         self._frames = frames
@@ -210,7 +224,7 @@ class FakeCapture:
             return False, None
         f = self._frames[self._i]
         self._i += 1
-        if f.ndim == 2:
+        if f.ndim == 2 and f.dtype != np.uint16:
             f = np.repeat(f[:, :, None], 3, axis=2)
         return True, f
 

@@ -31,6 +31,29 @@ def float_to_uint8(img):
     return device.like_input(dst, img)
 
 
+def uint16_to_float(img):
+    """The 16-bit counterpart of uint8_to_float (ours; the reference has no 16-bit path): img * (1./65535) as float64, one
+    multiplication by the rounded constant (rm_uint16_to_float).  It is the number every kernel makes of a uint16 pixel."""
+    t = device.require_gpu()
+    lib = _capi.load()
+    src = device.to_device(img, t.uint16)
+    dst = t.empty(src.shape, dtype=t.float64, device=src.device)
+    _capi.check(lib, lib.rm_uint16_to_float(device.ctx(), device.ptr(src), device.ptr(dst), src.numel(), device.stream_ptr()),
+                "rm_uint16_to_float")
+    return device.like_input(dst, img)
+
+
+def float_to_uint16(img):
+    """The 16-bit counterpart of float_to_uint8: img*65535 stored into uint16 (C truncation, low 16 bits; NaN -> 0)."""
+    t = device.require_gpu()
+    lib = _capi.load()
+    src = device.to_device(img, t.float64)
+    dst = t.empty(src.shape, dtype=t.uint16, device=src.device)
+    _capi.check(lib, lib.rm_float_to_uint16(device.ctx(), device.ptr(src), device.ptr(dst), src.numel(), device.stream_ptr()),
+                "rm_float_to_uint16")
+    return device.like_input(dst, img)
+
+
 def bgr_buffer_to_gray(buf):
     """[T,H,W,3] uint8 -> [T,H,W] uint8: cv2.cvtColor(BGR2GRAY) of every frame (base.py:230) on the device (rm_bgr_to_gray) -- what the
     calibration kernels do on the fly with an RM_BGR8 buffer, for the entry points that take gray frames."""
@@ -264,9 +287,10 @@ def eulerian_magnification_video(vid_data, fps, freq_min, freq_max, amplificatio
     Laplacian pyramid, transforms.py:181 is the commented-out collapse of it.  [T,H,W] = frame + raw_bandpassed_data (what
     eulerian_magnification_bandpass returns second), one float64 addition per pixel, formed in one fused pass over the frame buffer
     (rm_magnify) without a [T,H,W] float64 intermediate.
-    `vid_data`: [T,H,W] uint8 / float16 / float32 / float64 or [T,H,W,3] uint8 BGR; numpy in -> numpy out, device tensor in -> device
-    tensor out.  `out_dtype`: 'uint8' (clamped to [0, 1] first, then float_to_uint8's truncation -- the clamp is this library's),
-    'float32' or 'float64' (numpy / torch dtypes are accepted too); None: uint8 for uint8 and BGR input, float64 otherwise.
+    `vid_data`: [T,H,W] uint8 / uint16 / float16 / float32 / float64 or [T,H,W,3] uint8 BGR; numpy in -> numpy out, device tensor in ->
+    device tensor out.  `out_dtype`: 'uint8' (clamped to [0, 1] first, then float_to_uint8's truncation -- the clamp is this library's),
+    'uint16' (the same clamp, then float_to_uint16's truncation), 'float32' or 'float64' (numpy / torch dtypes are accepted too); None:
+    uint8 for uint8 and BGR input, uint16 for uint16 input, float64 otherwise.
     `color=True` (rm_magnify_bgr): `vid_data` must be a [T,H,W,3] uint8 BGR buffer and the result is the [T,H,W,3] uint8 BGR video with
     the same band-passed motion (that of the gray image) added to the three channels -- luma magnified, chroma left alone; `out_dtype`
     None or uint8.  The default gives the gray video, also for BGR input."""
@@ -289,12 +313,13 @@ def eulerian_magnification_video(vid_data, fps, freq_min, freq_max, amplificatio
                                             device.stream_ptr()), "rm_magnify_bgr")
         return device.like_input(out, vid_data)
     if out_dtype is None:
-        out_dtype = "uint8" if vid.dtype == t.uint8 else "float64"
+        out_dtype = "uint8" if vid.dtype == t.uint8 else "uint16" if vid.dtype == t.uint16 else "float64"
     name = dtype_name(out_dtype)
     code = device.buffer_dtype_code(vid)
-    table = {"uint8": (t.uint8, _capi.RM_U8), "float32": (t.float32, _capi.RM_F32), "float64": (t.float64, _capi.RM_F64)}
+    table = {"uint8": (t.uint8, _capi.RM_U8), "uint16": (t.uint16, _capi.RM_U16), "float32": (t.float32, _capi.RM_F32),
+             "float64": (t.float64, _capi.RM_F64)}
     if name not in table:
-        raise TypeError("out_dtype must be uint8, float32 or float64, got %r" % (out_dtype,))
+        raise TypeError("out_dtype must be uint8, uint16, float32 or float64, got %r" % (out_dtype,))
     out = t.empty((T, H, W), dtype=table[name][0], device=vid.device)
     _capi.check(lib, lib.rm_magnify(device.ctx(), device.ptr(vid), code, T, H, W, float(fps), float(freq_min), float(freq_max),
                                     float(amplification), int(pyramid_levels), int(skip_levels_at_top), device.ptr(out), table[name][1],

@@ -71,7 +71,7 @@ class SlidingCalibration:
 
     # ------------------------------------------------------------------ frames in
     def push(self, frames, bgr=False):
-        """One frame [H,W] or many [n,H,W] of uint8 / float16 / float32 / float64 (the values uint8_to_float gives, as in a calibration
+        """One frame [H,W] or many [n,H,W] of uint8 / uint16 / float16 / float32 / float64 (the values uint8_to_float gives, as in a calibration
         buffer of that dtype); with bgr=True, BGR frames as captured: uint8 [H,W,3] or [n,H,W,3].  numpy or device tensor;
         asynchronous.  Successive pushes may differ in dtype.  Returns the number of frames pushed."""
         x = device.to_device(frames)
