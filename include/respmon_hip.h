@@ -445,6 +445,68 @@ int rm_stream_reset(rm_ctx *ctx, rm_stream *st);
 int rm_stream_info(const rm_stream *st, long long *frames_seen, size_t *np, size_t *state_bytes);
 int rm_stream_push(rm_ctx *ctx, rm_stream *st, const void *frames_dev, int dtype, int n, void *out_dev, int out_dtype, void *stream);
 
+/* ---- PHASE-BASED motion magnification on the Riesz pyramid (Wadhwa, Rubinstein, Durand, Freeman, "Riesz Pyramids for Fast Phase-Based
+ *      Video Magnification", ICCP 2014), a stream object like rm_stream.  The linear method (rm_magnify, rm_stream_*) adds
+ *      amplification * band-passed intensity: it holds only while amplification * displacement is small against the spatial
+ *      wavelength, amplifies sensor noise by the same factor and leaves [0, 1].  Here the local PHASE of every processed Laplacian
+ *      level is band-passed and the level is shifted by amplification * that phase: larger motions, no intensity overshoot, and no
+ *      start-up ringing, because the filtered quantity (the accumulated phase difference) starts at zero.
+ *      Definition.  THE ORDER OF OPERATIONS IS PART OF THE INTERFACE.  Everything is float64 and every operation rounds once.  Let
+ *      L_l[t] be level l of the Laplacian pyramid of frame t, exactly what rm_create_laplacian_video_pyramid produces (levels
+ *      0 .. pyramid_levels-1).  Processed levels are skip_levels_at_top <= l <= pyramid_levels - 2; all other levels, the low-pass
+ *      residual included, pass through unchanged.  For a processed level, frame t counted since create or reset, pixel (y, x), I = L_l[t]:
+ *          R1 = 0.5*(I[y][x+1] - I[y][x-1])      R2 = 0.5*(I[y+1][x] - I[y-1][x])
+ *                  neighbour indices by BORDER_REFLECT_101; an axis of length 1 gives 0
+ *          first frame after create/reset:  dc = ds = 0
+ *          otherwise, with (Ip, R1p, R2p) of the previous frame:
+ *              re  = (I*Ip + R1*R1p) + R2*R2p
+ *              qx  = Ip*R1 - I*R1p          qy = Ip*R2 - I*R2p
+ *              hyp = sqrt(qx*qx + qy*qy)    d  = atan2(hyp, re)
+ *              dc  = hyp > 0 ? d*(qx/hyp) : 0       ds = hyp > 0 ? d*(qy/hyp) : 0
+ *          Pc += dc;  Ps += ds                         (both start at 0)
+ *          A   = sqrt((I*I + R1*R1) + R2*R2)
+ *          Fc  = sosfilt step of Pc,  Fs = sosfilt step of Ps
+ *                  rm_sosfilt's operation order, from rest, scale 1
+ *          den = B(A)    nc = B(A*Fc)    ns = B(A*Fs)
+ *                  B is the separable 9-tap binomial (1,8,28,56,70,56,28,8,1)/256:
+ *                  along x first, then along y; each pass is the left-to-right sum of k[i]*v[i];
+ *                  indices reflected 101 repeatedly (period 2(n-1)); an axis of length 1 reads index 0
+ *          bc  = den > 0 ? nc/den : 0       bs = den > 0 ? ns/den : 0
+ *                  with RM_PHASE_NO_BLUR: bc = Fc, bs = Fs
+ *          m   = sqrt(bc*bc + bs*bs)   am = amplification*m   c = cos(am)   s = sin(am)
+ *          ux  = m > 0 ? bc/m : 0      uy = m > 0 ? bs/m : 0
+ *          L'_l[t] = I*c - (R1*ux + R2*uy)*s
+ *      Then
+ *          out[t] = convert( rm_collapse_laplacian_video_pyramid's rule applied to L' )
+ *      atan2(hyp, re) stands where the paper writes acos(re/|q|): the same value, well conditioned near zero phase.  Consequences:
+ *      the first frame comes back as the collapse of its own pyramid; the result for a sequence does not depend on how it was cut
+ *      into pushes (on one device bit for bit); skip_levels_at_top >= pyramid_levels - 1 processes nothing (no state; a push is
+ *      pyramid, collapse, conversion).
+ *      Known limits: the three-tap Riesz pair (R1, R2) is exact only near spatial frequency pi/2; the phase blur averages across
+ *      orientations.  A numpy prototype delivers 0.74-0.85 of the nominal (1 + amplification) on oriented structure, about 0.65 on
+ *      isotropic texture with the blur and about 0.85 without (prototype figures).
+ *      rm_phase_create: sos_host[nsec][6], 1 <= nsec <= 8, checked as rm_sosfilt checks them (RM_E_BADARG: nsec < 1, a section with
+ *        a0 != 1, NULL pointers, H, W or pyramid_levels < 1, skip_levels_at_top < 0, unknown flags; RM_E_UNSUPPORTED: nsec > 8, more than
+ *        16 processed levels).  The state is (5 + 4 * nsec) * NP doubles -- Ip, R1p, R2p, Pc, Ps and the two filters' states --, NP the
+ *        pixels of the processed levels of one frame, its own allocation on the context's device.
+ *      rm_phase_push: n >= 1 gray frames [n,H,W] of dtype RM_U8 / RM_U16 / RM_F16 / RM_F32 / RM_F64 -> out_dev[n,H,W] of out_dtype RM_F64 /
+ *        RM_F32 / RM_U8 / RM_U16 with rm_magnify's conversions (the clamp to [0, 1] and the truncation of the integer outputs included).
+ *        RM_BGR8 frames: RM_E_UNSUPPORTED (colour is out of scope).  RM_E_BADARG: n < 1, NULL pointers, any other dtype or out_dtype,
+ *        out_dev overlapping the frames, an object created on another device; nothing is written on a refusal.  Asynchronous on
+ *        `stream`; n is unbounded (a call whose workspace would pass 2 GiB is split internally; the number of launches of one such
+ *        piece depends on the pyramid alone, not on its frames).  Pushes of one object belong on one stream.  Uses the context's
+ *        workspace: RM_E_BUSY as rm_stream_push.
+ *      rm_phase_reset: the next push starts a new sequence.  rm_phase_info: frames pushed since creation / reset, NP, bytes of state
+ *        (any pointer may be NULL).  rm_phase_destroy waits for the device work that uses the state. */
+typedef struct rm_phase rm_phase;
+#define RM_PHASE_NO_BLUR 1u
+int rm_phase_create(rm_ctx *ctx, int H, int W, int pyramid_levels, int skip_levels_at_top, const double *sos_host, int nsec,
+                    double amplification, unsigned flags, rm_phase **out);
+int rm_phase_destroy(rm_phase *ph);
+int rm_phase_reset(rm_ctx *ctx, rm_phase *ph);
+int rm_phase_info(const rm_phase *ph, long long *frames_seen, size_t *np, size_t *state_bytes);
+int rm_phase_push(rm_ctx *ctx, rm_phase *ph, const void *frames_dev, int dtype, int n, void *out_dev, int out_dtype, void *stream);
+
 /* ---- base.py:355-358 + 471: extract_motion('average') = np.average(frame[y:y+h, x:x+w]) -- */
 int rm_roi_mean(rm_ctx *ctx, const void *frame_dev, int dtype, int H, int W, int x, int y, int w, int h,
                 double *out_host, void *stream);

@@ -26,7 +26,7 @@ extern "C" {
  * "flow_clip_bytes" n lowers the workspace cap of one chunk of rm_flow_clip and rm_flow_multi_clip (0: 256 MiB), so that a test splits
  * a small clip into several chunks: a chunk holds max(1, n / slot - 1) frames, slot = 5 bytes per pixel of every LK pyramid level of
  * the ROI -- for rm_flow_multi_clip the sum of that over the subjects that still have points.
- * "stream_frames" n: frames per internal chunk of rm_stream_push (0: by its workspace cap of 256 MiB, at most 256), so that a test
+ * "stream_frames" n: frames per internal chunk of rm_stream_push and rm_phase_push (0: by their workspace caps of 256 MiB / 2 GiB, at most 256), so that a test
  * reaches the split with a handful of frames.
  * "rate_wide" 0|1: the K-split / the wave-per-16-columns form of the rate map's kernel whatever the level size (-1: by size). */
 int rm_debug_set(rm_ctx *ctx, const char *key, long long value);

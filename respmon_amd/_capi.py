@@ -31,6 +31,7 @@ RM_FLAG_FILTER_LAPLACIANS = 64
 RM_FLAG_DENSE_SUM = 128
 RM_FLAG_SPARSE_SUM = 256
 RM_FLAG_FF_PER_LEVEL = 512
+RM_PHASE_NO_BLUR = 1   # rm_phase_create: the band-passed phase is used as it is (no amplitude-weighted blur)
 
 _c = ctypes
 _vp, _i, _d, _sz, _u = _c.c_void_p, _c.c_int, _c.c_double, _c.c_size_t, _c.c_uint
@@ -108,6 +109,11 @@ SIGNATURES = {
     "rm_stream_reset": (_i, [_vp, _vp]),
     "rm_stream_info": (_i, [_vp, _c.POINTER(_c.c_longlong), _c.POINTER(_sz), _c.POINTER(_sz)]),
     "rm_stream_push": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
+    "rm_phase_create": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _d, _u, _c.POINTER(_vp)]),
+    "rm_phase_destroy": (_i, [_vp]),
+    "rm_phase_reset": (_i, [_vp, _vp]),
+    "rm_phase_info": (_i, [_vp, _c.POINTER(_c.c_longlong), _c.POINTER(_sz), _c.POINTER(_sz)]),
+    "rm_phase_push": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "rm_roi_mean": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_roi_to_uint8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_good_features_to_track": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp]),

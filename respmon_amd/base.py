@@ -766,13 +766,28 @@ class RespiratoryMonitor(BreathSignal):
 
     calibrate = locate  # north_star names a calibrate(); the reference's calibration entry is locate()
 
-    def magnified_calibration_video(self, out_dtype=None, color=False):
+    def magnified_calibration_video(self, out_dtype=None, color=False, method='linear', amplification=None):
         """The current calibration buffer with its breathing motion amplified -- what locate() looks at, frame by frame: the frames plus
         the band-passed signal of locate()'s defaults (amplification 500, pyramid_levels 9, skip_levels_at_top 4) at the monitor's fps,
         freq_min and freq_max (transforms.eulerian_magnification_video).  A device tensor [T,H,W]; `out_dtype` None: uint8 for a uint8 or
         'bgr8' buffer, uint16 for a uint16 one, float64 otherwise.  `color=True` (buffer_dtype 'bgr8' only): the frames as captured with
-        that motion laid over them, [T,H,W,3] uint8 BGR."""
+        that motion laid over them, [T,H,W,3] uint8 BGR.
+        `method='phase'`: the buffer through transforms.phase_magnification_video instead (phase-based magnification on the Riesz pyramid
+        at the monitor's fps and band, its own defaults otherwise: `amplification` 10 unless given, pyramid_levels 5, every level but
+        the residual processed); gray only -- a 'bgr8' buffer is converted first, color=True is refused.  `amplification` is read by
+        this method alone."""
         from .transforms import eulerian_magnification_video
+        if method == 'phase':
+            from .transforms import bgr_buffer_to_gray, phase_magnification_video
+            if color:
+                raise ValueError("magnified_calibration_video(method='phase') is gray only (color=True is not supported)")
+            buf = self.calibration_buffer
+            if device.is_bgr_buffer(buf):
+                buf = bgr_buffer_to_gray(buf)
+            return phase_magnification_video(buf, self.fps, self.freq_min, self.freq_max, 10 if amplification is None else amplification,
+                                             out_dtype=out_dtype)
+        if method != 'linear':
+            raise ValueError("method must be 'linear' or 'phase', got %r" % (method,))
         if color and not device.is_bgr_buffer(self.calibration_buffer):
             raise ValueError("magnified_calibration_video(color=True) needs buffer_dtype='bgr8'; this monitor's buffer_dtype is %r"
                              % (getattr(self, "buffer_dtype", str(self.calibration_buffer.dtype).replace("torch.", "")),))

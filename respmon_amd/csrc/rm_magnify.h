@@ -114,7 +114,7 @@ template <> struct MagGeom<bgr8_t, bgr8_t> {   // colour: 16 pixels = 48 bytes p
     static constexpr int C = 3, V = 16, NP = CT_H * CT_W / (64 * V), NE = V * C;
 };
 template <typename Tin, typename Tout> constexpr bool mag_colour = false;
-template <> constexpr bool mag_colour<bgr8_t, bgr8_t> = true;
+template <> inline constexpr bool mag_colour<bgr8_t, bgr8_t> = true;   // (inline: rm_phase_kernels.h includes this header for mag_out, a second unit)
 
 // the V pixels of one lane and pass, as stored
 template <typename Tin, typename Tout> struct MagIn { typename MagGeom<Tin, Tout>::E e[MagGeom<Tin, Tout>::NE]; };

@@ -18,10 +18,12 @@ DEFAULT = os.path.join(ROOT, "respmon_amd", "csrc", "build_resources.txt")
 # ... and the per-clip LK tracker (rm_flow_multi.h): its wave walks all frames of a chunk, scratch would be paid once per frame and point
 # ... and the live stream (rm_stream.hip): k_sosfilt keeps the 2 x nsec state values of its element in registers over a whole call, and the
 #     SYM = 0 instances of k_magnify (one frame tile in flight) fall under the k_magnify pattern with the SYM = 1 ones
+# ... and phase-based magnification (rm_phase.hip): k_phase_time keeps 5 + 4 nsec state values of its pixel in registers over a whole push,
+#     k_phase_space streams three planes per frame
 # ... and the multi-subject ROI mean (rm_subjects.h): a workgroup per (frame, subject) pair streams its rectangle once
 MUST_NOT_SPILL = re.compile(r"^(void )?rm::k_down_chain<[^>]*, false>|^(void )?rm::k_down_chain_stitch<|^(void )?rm::k_down_chain_u8<|^(void )?rm::k_down_chain_narrow<|"
                             r"^(void )?rm::k_magnify<|^(void )?rm::k_roi_mean_multi_clip<|"
-                            r"^(void )?rm::k_lk_track_multi_clip<|^(void )?rm::k_sosfilt<")
+                            r"^(void )?rm::k_lk_track_multi_clip<|^(void )?rm::k_sosfilt<|^(void )?rm::k_phase_time<|^(void )?rm::k_phase_space<")
 # kernels (mangled names, as the report spells them) that may be compiled in more than one unit, each with its reason.  None: wherever
 # several units need a kernel, one of them holds a launcher for it (launch_state_init, threshold_mask, launch_heat_minmax, ...).
 MAY_REPEAT = set()
