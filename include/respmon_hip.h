@@ -507,6 +507,66 @@ int rm_phase_reset(rm_ctx *ctx, rm_phase *ph);
 int rm_phase_info(const rm_phase *ph, long long *frames_seen, size_t *np, size_t *state_bytes);
 int rm_phase_push(rm_ctx *ctx, rm_phase *ph, const void *frames_dev, int dtype, int n, void *out_dev, int out_dtype, void *stream);
 
+/* ---- the 'PHASE' motion signal of extract_motion: the amplitude-weighted mean phase velocity of an ROI.  The ROI mean ('average')
+ *      sees brightness changes, the Lucas-Kanade tracks ('flow') need corners; a chest under a blanket, on an infrared or depth
+ *      camera, moves a fraction of a pixel at constant brightness and offers texture only.  The quaternionic phase difference of a
+ *      Riesz-pyramid level between consecutive frames -- the quantity rm_phase_* shifts a level by -- measures exactly that.
+ *      Definition.  THE ORDER OF OPERATIONS IS PART OF THE INTERFACE.  Everything is float64 and every operation rounds once.  A
+ *      session rm_phase_motion belongs to one rectangle size (w, h) and one pyramid level l, 0 <= l <= 8.  For frame t, counted since
+ *      create or reset, and the rectangle (x, y, w, h):
+ *          C  = the float64 crop frame[y:y+h, x:x+w], converted from the buffer dtype as the pyramid entry points convert it
+ *               (RM_U8: k*(1./255), RM_U16: k*(1./65535), RM_F16 / RM_F32 widened, RM_F64 as it is)
+ *          I  = level l of rm_create_laplacian_video_pyramid applied to C as a [1,h,w] clip with pyramid_levels = l + 2:
+ *               G_0 = C, G_k+1 = pyrDown(G_k), I = G_l - pyrUp(G_l+1).  The crop is an image of its own: borders reflect at the
+ *               crop's edge, as in the flow path.  I is lh x lw, lh = h and lw = w halved l times, rounding up.
+ *          R1 = 0.5*(I[y][x+1] - I[y][x-1])      R2 = 0.5*(I[y+1][x] - I[y-1][x])
+ *                  neighbour indices by BORDER_REFLECT_101; an axis of length 1 gives 0
+ *          A  = sqrt((I*I + R1*R1) + R2*R2)
+ *          t == 0:  Sw = Sc = Ss = 0
+ *          otherwise, with (Ip, R1p, R2p, Ap) of the previous frame, per pixel:
+ *              re  = (I*Ip + R1*R1p) + R2*R2p
+ *              qx  = Ip*R1 - I*R1p          qy = Ip*R2 - I*R2p
+ *              hyp = sqrt(qx*qx + qy*qy)    d  = atan2(hyp, re)
+ *              dc  = hyp > 0 ? d*(qx/hyp) : 0       ds = hyp > 0 ? d*(qy/hyp) : 0
+ *              wgt = A*Ap
+ *          Sw = sum wgt     Sc = sum wgt*dc     Ss = sum wgt*ds      over the pixels of the level
+ *      The order of the three sums is the implementation's; it is a function of (lh, lw) alone, never of N, K, the chunking, the
+ *      frame's position in a call or the other subjects (here: 64 x 4 tiles, a DPP wave reduction per row, the four rows in order,
+ *      the tiles in order).  Outputs per frame: the three sums.  The caller forms v = (Sc/Sw, Ss/Sw) when Sw > 0: the mean phase
+ *      velocity in radians per frame at level l, positive for content moving toward +x / +y.  It is not pixels: a numpy prototype
+ *      measures 0.2-0.4 rad per frame and pixel on broadband texture, depending on level and content; the nominal pi/2 / 2^l holds
+ *      only at spatial frequency pi/2.
+ *      rm_phase_motion_create: the state is 2 * lh * lw doubles -- the previous frame's I (R1p, R2p, Ap are recomputed from it) in two
+ *        planes that the internal chunks alternate between --, its own allocation on the context's device (rm_phase_motion_info reports
+ *        frames seen, lh, lw, bytes; any pointer may be NULL).  RM_E_BADARG: NULL pointers, w or h < 1, level < 0; RM_E_UNSUPPORTED:
+ *        level > 8.
+ *      rm_phase_motion_clip: N >= 1 gray frames [N,H,W] resident on the device, the rectangle at (x, y) with the state's size ->
+ *        sums_host[N][3] = Sw, Sc, Ss per frame.  N == 1 is the per-frame step; there is no separate begin: the first frame after
+ *        create or reset returns zeros and becomes the state.  A clip may be cut anywhere, bit for bit.  It is the K == 1 case of
+ *      rm_phase_motion_multi_clip: K subjects, subject k on states_host[k] with rectangle rois_host[k] (x, y, w, h; levels may differ)
+ *        -> sums_host[N][K][3]; exactly K rm_phase_motion_clip calls, bit for bit, in outputs and in the states it leaves, so single and
+ *        multi calls may be mixed on a state.  Rectangles may overlap or repeat (each with its own state).  The subjects share every
+ *        launch: the front (crop with its conversion, the pyrDown chain to G_l+1, the level) runs over (pixel block, frame, subject);
+ *        in the reduction a lane owns a level pixel and walks the frames of a chunk with the previous frame in registers.  The
+ *        launches of a chunk grow with the level only; a call makes one table upload, one result copy and one stream wait.  The
+ *        workspace holds crop-sized planes only, 256 MiB at most summed over the subjects (longer clips are chunked internally),
+ *        and belongs to the context: RM_E_BUSY as rm_stream_push.
+ *        Refusal is all or nothing -- nothing is enqueued, no state is touched, no output is written; the error text names the first
+ *        offending subject.  RM_E_BADARG: K outside 1..RM_MAX_ROIS, N < 1, NULL pointers (a NULL entry of states_host included), a
+ *        dtype that is no gray frame dtype, a rectangle outside the frame or of another size than its state, a state of another
+ *        device, the same state twice.  RM_E_UNSUPPORTED: RM_BGR8 frames.
+ *      rm_phase_motion_reset: the next frame starts a new sequence.  rm_phase_motion_destroy waits for the device work that uses the
+ *        state. */
+typedef struct rm_phase_motion rm_phase_motion;
+int rm_phase_motion_create(rm_ctx *ctx, int w, int h, int level, rm_phase_motion **out);
+int rm_phase_motion_destroy(rm_phase_motion *st);
+int rm_phase_motion_reset(rm_ctx *ctx, rm_phase_motion *st);
+int rm_phase_motion_info(const rm_phase_motion *st, long long *frames_seen, int *lh, int *lw, size_t *state_bytes);
+int rm_phase_motion_clip(rm_ctx *ctx, rm_phase_motion *st, const void *frames_dev, int dtype, int N, int H, int W, int x, int y,
+                         double *sums_host /* [N][3]: Sw, Sc, Ss */, void *stream);
+int rm_phase_motion_multi_clip(rm_ctx *ctx, rm_phase_motion *const *states_host /* [K] */, const void *frames_dev, int dtype, int N, int H, int W,
+                               const int32_t *rois_host /* [K][4] x,y,w,h */, int K, double *sums_host /* [N][K][3] */, void *stream);
+
 /* ---- base.py:355-358 + 471: extract_motion('average') = np.average(frame[y:y+h, x:x+w]) -- */
 int rm_roi_mean(rm_ctx *ctx, const void *frame_dev, int dtype, int H, int W, int x, int y, int w, int h,
                 double *out_host, void *stream);

@@ -28,6 +28,8 @@ extern "C" {
  * the ROI -- for rm_flow_multi_clip the sum of that over the subjects that still have points.
  * "stream_frames" n: frames per internal chunk of rm_stream_push and rm_phase_push (0: by their workspace caps of 256 MiB / 2 GiB, at most 256), so that a test
  * reaches the split with a handful of frames.
+ * "phase_motion_frames" n: frames per internal chunk of rm_phase_motion_clip and rm_phase_motion_multi_clip at most (0: by their 256 MiB
+ * workspace cap), so that a test reaches the split -- and the alternation of the state's two planes -- with a handful of frames.
  * "rate_wide" 0|1: the K-split / the wave-per-16-columns form of the rate map's kernel whatever the level size (-1: by size). */
 int rm_debug_set(rm_ctx *ctx, const char *key, long long value);
 

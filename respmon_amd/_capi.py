@@ -114,6 +114,12 @@ SIGNATURES = {
     "rm_phase_reset": (_i, [_vp, _vp]),
     "rm_phase_info": (_i, [_vp, _c.POINTER(_c.c_longlong), _c.POINTER(_sz), _c.POINTER(_sz)]),
     "rm_phase_push": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
+    "rm_phase_motion_create": (_i, [_vp, _i, _i, _i, _c.POINTER(_vp)]),
+    "rm_phase_motion_destroy": (_i, [_vp]),
+    "rm_phase_motion_reset": (_i, [_vp, _vp]),
+    "rm_phase_motion_info": (_i, [_vp, _c.POINTER(_c.c_longlong), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_sz)]),
+    "rm_phase_motion_clip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "rm_phase_motion_multi_clip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "rm_roi_mean": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_roi_to_uint8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_good_features_to_track": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp]),

@@ -54,6 +54,33 @@ class FlowState:
             pass
 
 
+class PhaseMotionState:
+    """Owner of one rm_phase_motion (the session of extract_motion('phase'): the previous frame's pyramid level of one rectangle size);
+    released with the object."""
+
+    def __init__(self, lib, w, h, level):
+        import ctypes
+        self._lib = lib
+        self.w, self.h, self.level = int(w), int(h), int(level)
+        self.handle = ctypes.c_void_p()
+        _capi.check(lib, lib.rm_phase_motion_create(device.ctx(), self.w, self.h, self.level, ctypes.byref(self.handle)), "rm_phase_motion_create")
+
+    def reset(self):
+        """The next frame begins a new sequence: it returns zeros and becomes the state."""
+        _capi.check(self._lib, self._lib.rm_phase_motion_reset(device.ctx(), self.handle), "rm_phase_motion_reset")
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self._lib.rm_phase_motion_destroy(self.handle)
+            self.handle.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
 class _Backend:
     """The only door from the state machine to compute: every method is one C-ABI call.
     Tests of the host logic replace it with a recording double; there is no CPU implementation."""
@@ -365,6 +392,37 @@ class _Backend:
                                                           ctypes.c_void_p(ng.ctypes.data), device.stream_ptr()), "rm_flow_multi_clip")
         return mean, ng
 
+    # -- extract_motion('phase'): the phase sums of a rectangle, per frame (a clip of one) or per clip, for one or several subjects ------
+    def phase_motion_state(self, w, h, level):
+        """A new rm_phase_motion on the current device for w x h rectangles at pyramid level `level`."""
+        return PhaseMotionState(self.lib, w, h, level)
+
+    def phase_motion_clip(self, state, frames, x, y):
+        """ndarray [N, 3]: Sw, Sc, Ss of every frame of the resident [N,H,W] clip for the state's rectangle at (x, y), one call."""
+        import ctypes
+        frames = frames.contiguous()
+        N, H, W = frames.shape
+        out = np.empty((N, 3), dtype=np.float64)
+        _capi.check(self.lib, self.lib.rm_phase_motion_clip(device.ctx(), state.handle, device.ptr(frames), device.dtype_code(frames), N, H, W,
+                                                            int(x), int(y), ctypes.c_void_p(out.ctypes.data), device.stream_ptr()),
+                    "rm_phase_motion_clip")
+        return out
+
+    def phase_motion_multi_clip(self, states, frames, rois):
+        """ndarray [N, K, 3]: phase_motion_clip of subject k on states[k] with rectangle rois[k], in one call."""
+        import ctypes
+        frames = frames.contiguous()
+        N, H, W = frames.shape
+        r = np.ascontiguousarray(rois, dtype=np.int32).reshape(-1, 4)
+        K = len(r)
+        assert len(states) == K, "one phase state per rectangle"
+        handles = (ctypes.c_void_p * K)(*[st.handle for st in states])
+        out = np.empty((N, K, 3), dtype=np.float64)
+        _capi.check(self.lib, self.lib.rm_phase_motion_multi_clip(device.ctx(), handles, device.ptr(frames), device.dtype_code(frames), N, H, W,
+                                                                  ctypes.c_void_p(r.ctypes.data), K, ctypes.c_void_p(out.ctypes.data),
+                                                                  device.stream_ptr()), "rm_phase_motion_multi_clip")
+        return out
+
     def pca_reduce_windows_multi(self, rows_list, firsts, window):
         """[pca_reduce_windows(rows_list[k], firsts[k], window) for every k], in one call."""
         import ctypes
@@ -389,7 +447,8 @@ class RespiratoryMonitor(BreathSignal):
 
     def __init__(self, capture_target=0, save_calibration_image=False, visualize='pyqtgraph', fig_size=None,
                  fps_limit=10, error_reset_delay=10.0, save_all_data=True,
-                 motion_extraction_method='average', buffer_dtype='float64', run_on_init=True, backend=None, relocate_every=0):
+                 motion_extraction_method='average', buffer_dtype='float64', run_on_init=True, backend=None, relocate_every=0,
+                 phase_params=None):
         """Arguments as reference base.py:24-34, plus (not in the reference):
         buffer_dtype -- element type of the calibration buffer in HBM: 'float64' (the reference's, base.py:119), 'float32',
             'float16', 'uint8' (the gray frame as ingested; uint8_to_float happens where the buffer is read), 'uint16' (the same for
@@ -400,6 +459,11 @@ class RespiratoryMonitor(BreathSignal):
             [T,H,W,3] uint8 buffer of the frames AS CAPTURED: cvtColor + uint8_to_float happen where the buffer is read; next_frame()
             keeps the device copy of the captured frame for step(), a frame from anywhere else is stored as its gray value in
             three planes -- the same calibration either way);
+        motion_extraction_method -- 'average' and 'flow' are the reference's; 'phase' (not in the reference) measures the
+            amplitude-weighted mean phase velocity of one Riesz-pyramid level of the ROI (include/respmon_hip.h rm_phase_motion_*): the
+            signal for a region that moves a fraction of a pixel at constant brightness and offers texture, not corners.  A frame
+            yields a 2-vector as the flow path's mean flow does, and goes through the same motion_data / PCA bookkeeping;
+            phase_params -- dict(level=1): the pyramid level (0 .. 8) of the 'phase' method;
         run_on_init -- False: construct without entering run(); backend -- a stand-in for the device backend (tests);
         relocate_every -- 0 (default): the reference's one-shot calibration buffer, nothing else.  n > 0: every frame that is stored or
             measured also goes into a sliding window on the device (respmon_amd/window.py SlidingCalibration: a ring of per-frame
@@ -422,7 +486,7 @@ class RespiratoryMonitor(BreathSignal):
         assert isinstance(error_reset_delay, (int, float)) and error_reset_delay >= 0, \
             "error_reset_delay must be a positive int or float"
         assert isinstance(save_all_data, bool), "save_all_data should be bool"
-        assert motion_extraction_method in ("average", "flow"), "motion_extraction_method must be 'average' or 'flow'"
+        assert motion_extraction_method in ("average", "flow", "phase"), "motion_extraction_method must be 'average', 'flow' or 'phase'"
         assert buffer_dtype in ("float64", "float32", "float16", "uint8", "uint16", "bgr8")
         assert isinstance(relocate_every, int) and relocate_every >= 0, "relocate_every must be a non-negative int"
 
@@ -458,6 +522,9 @@ class RespiratoryMonitor(BreathSignal):
         self.feature_params = dict(maxCorners=100, qualityLevel=0.3, minDistance=7, blockSize=7)
         self.lk_params = dict(winSize=(15, 15), maxLevel=2,
                               criteria=(self.TERM_CRITERIA_EPS | self.TERM_CRITERIA_COUNT, 10, 0.03))
+        self.phase_params = dict(level=1)
+        self.phase_params.update(phase_params or {})
+        self._phase_state, self._phase_begun = None, False
         self.gaussian_cutoff = 10.0
         self.filter_order = 3
         self.peak_minimum_sample_distance = 0
@@ -594,6 +661,7 @@ class RespiratoryMonitor(BreathSignal):
         self.calibration_buffer_idx = 0
         self.previous_cropped_image = None
         self.motion_key_points = None
+        self._phase_state, self._phase_begun = None, False
 
     def sync_to_fps(self):
         """base.py:535-541."""
@@ -615,6 +683,8 @@ class RespiratoryMonitor(BreathSignal):
         if self.motion_extraction_method == "average":
             return self._backend.roi_mean(self._frame_u8, x, y, w, h)       # np.average(crop), base.py:357
         be = self._backend
+        if self.motion_extraction_method == "phase":
+            return self._extract_motion_phase(be, x, y, w, h)
         if self.fused_flow_step and hasattr(be, "flow_step"):
             return self._extract_motion_flow_resident(be, x, y, w, h)
         if self.previous_cropped_image is None:                            # base.py:363-369
@@ -669,6 +739,42 @@ class RespiratoryMonitor(BreathSignal):
         if len(self.motion_data) >= 2:
             return be.pca_reduce(np.array(self.motion_data, dtype=np.float32))  # base.py:396-405
         return 0.0
+
+    # 'phase': one rm_phase_motion_clip call of N == 1 per frame on a session the monitor owns.  The session's first frame only becomes
+    # its state (value 0.0); a frame without amplitude (Sw == 0) takes the path n_good == 0 takes in 'flow' mode; every other frame
+    # appends float32(v) to motion_data, and from the second row on the value is the PCA of the rows: the flow bookkeeping.
+    def _phase_session(self, be, w, h):
+        st = self._phase_state
+        if st is None or (st.w, st.h) != (w, h):
+            st = self._phase_state = be.phase_motion_state(w, h, int(self.phase_params["level"]))
+            self._phase_begun = False
+        return st
+
+    def _extract_motion_phase(self, be, x, y, w, h):
+        st = self._phase_session(be, w, h)
+        begins = not self._phase_begun
+        Sw, Sc, Ss = be.phase_motion_clip(st, self._frame_u8[None], x, y)[0]
+        self._phase_begun = True
+        if begins:
+            return 0.0
+        if not Sw > 0:
+            return np.nan
+        self.motion_data.append([np.float32(Sc / Sw), np.float32(Ss / Sw)])
+        if len(self.motion_data) >= 2:
+            return be.pca_reduce(np.array(self.motion_data, dtype=np.float32))
+        return 0.0
+
+    def _phase_clip_values(self, be, frames, x, y, w, h):
+        """The device work of a clip in 'phase' mode: one rm_phase_motion_clip call plus one rm_pca_reduce_windows call; returns
+        value(i) as _flow_clip_values does.  The session runs to the clip's end even if the replay stops at an error frame: reset()
+        discards it before measuring begins again."""
+        st = self._phase_session(be, w, h)
+        begins = not self._phase_begun
+        sums = be.phase_motion_clip(st, frames, x, y)
+        self._phase_begun = True
+        rows, first = self._phase_clip_rows(sums, begins)
+        pca = be.pca_reduce_windows(rows, first, self.measure_buffer_length) if len(rows) > first else []
+        return self._phase_clip_replay(sums, begins, pca)
 
     @property
     def motion_key_points(self):
@@ -854,7 +960,7 @@ class RespiratoryMonitor(BreathSignal):
 
     def step_clip(self, frames):
         """`for f in frames: step(f)` (each f being the current frame, as after next_frame()) with the device work of the 'measure'
-        state done per clip: one rm_roi_mean_clip call, or one rm_flow_clip plus one rm_pca_reduce_windows call, then the per-frame
+        state done per clip: one rm_roi_mean_clip call, or one rm_flow_clip / rm_phase_motion_clip plus one rm_pca_reduce_windows call, then the per-frame
         host bookkeeping replayed in order.  frames: [N,H,W] gray frames, a device tensor or a numpy array.  Returns the number of
         frames consumed: it stops behind the frame on which the state leaves 'measure'; frames met in any other state go through
         step() one by one."""
@@ -885,6 +991,14 @@ class RespiratoryMonitor(BreathSignal):
         if self.motion_extraction_method == "average":
             means = be.roi_mean_clip(frames, x, y, w, h)
             value_of = lambda i: float(means[i])
+        elif self.motion_extraction_method == "phase":
+            if len(self.motion_data) > self.measure_buffer_length:
+                for i in range(n):                                           # the per-frame calls (a deque longer than the popleft rule keeps it)
+                    self._step_frame(frames[i])
+                    if self.state != 'measure':
+                        return i + 1
+                return n
+            value_of = self._phase_clip_values(be, frames, x, y, w, h)
         else:
             begun = self.previous_cropped_image
             if (not self.fused_flow_step or not hasattr(be, "flow_clip") or (begun is not None and begun is not self._RESIDENT)
@@ -1009,6 +1123,10 @@ class RespiratoryMonitor(BreathSignal):
         if location is None:
             return
         roi = tuple(reduce_bounding_box(*location, self.maximum_bounding_box_area))
+        if roi != (self.x, self.y, self.w, self.h) and self.motion_extraction_method == "phase":
+            # the previous level and the velocities gathered so far belong to the old rectangle: the session is discarded
+            self._phase_state, self._phase_begun = None, False
+            self.motion_data.clear()
         if roi != (self.x, self.y, self.w, self.h) and self.motion_extraction_method == "flow":
             # the crop, its corners and the displacements gathered so far belong to the old rectangle: tracking begins again
             # (rm_flow_begin, or goodFeaturesToTrack on the four-call path) with the next frame

@@ -12,15 +12,14 @@ namespace rm {
 constexpr int PD_TY = 8, PD_TX = 64;
 constexpr int PD_SY = 2 * PD_TY + 3, PD_SX = 2 * PD_TX + 3;
 
+// the tile body: 256 threads stage rows 2 ty0 - 2 .. and columns 2 tx0 - 2 .. of ONE image `sp` (h x w, reflected 101) in s_src, filter along
+// x into s_row, then along y into the PD_TY x PD_TX outputs at (ty0, tx0) of `dp` (dh x dw).  A device function so that a kernel with
+// another block-to-image mapping (rm_phase_motion_kernels.h: pixel block, frame, subject) runs this arithmetic and no copy of it.
 template <typename Tin>
-__global__ __launch_bounds__(256) void k_pyr_down(const Tin *src, int h, int w, size_t frame_stride,
-                                                  double *dst, int dh, int dw)
+__device__ __forceinline__ void pyr_down_tile(const Tin *sp, int h, int w, double *dp, int dh, int dw, int ty0, int tx0,
+                                              double (&s_src)[PD_SY][PD_SX + 1], double (&s_row)[PD_SY][PD_TX])
 {
-    __shared__ double s_src[PD_SY][PD_SX + 1];
-    __shared__ double s_row[PD_SY][PD_TX];
     const int tid = threadIdx.x;
-    const int t = blockIdx.z, ty0 = blockIdx.y * PD_TY, tx0 = blockIdx.x * PD_TX;
-    const Tin *sp = src + (size_t)t * frame_stride;
     for (int i = tid; i < PD_SY * PD_SX; i += 256) {
         int r = i / PD_SX, c = i - r * PD_SX;
         int sy = reflect101(2 * ty0 - 2 + r, h), sx = reflect101(2 * tx0 - 2 + c, w);
@@ -40,9 +39,19 @@ __global__ __launch_bounds__(256) void k_pyr_down(const Tin *src, int h, int w, 
             int r = 2 * y;
             double v = (s_row[r + 2][x] * 6 + (s_row[r + 1][x] + s_row[r + 3][x]) * 4 + s_row[r][x] + s_row[r + 4][x]) *
                        (1.0 / 256);
-            dst[((size_t)t * dh + oy) * dw + ox] = v;
+            dp[(size_t)oy * dw + ox] = v;
         }
     }
+}
+
+template <typename Tin>
+__global__ __launch_bounds__(256) void k_pyr_down(const Tin *src, int h, int w, size_t frame_stride,
+                                                  double *dst, int dh, int dw)
+{
+    __shared__ double s_src[PD_SY][PD_SX + 1];
+    __shared__ double s_row[PD_SY][PD_TX];
+    const int t = blockIdx.z;
+    pyr_down_tile(src + (size_t)t * frame_stride, h, w, dst + (size_t)t * dh * dw, dh, dw, blockIdx.y * PD_TY, blockIdx.x * PD_TX, s_src, s_row);
 }
 
 // ----------------------------------------------------------------------------------------

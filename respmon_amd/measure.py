@@ -7,7 +7,7 @@ A user of the mixin provides: fps, freq_max, filter_order, gaussian_cutoff, peak
 measure_initialization_length, save_all_data, all_data, disable_error_detection, the deques data / t / freq, the list `buffers` of
 the deques the pop-left rule applies to, and -- unless disable_error_detection is set -- detect_errors() / trigger_error().
 For the 'flow' method's clips (_flow_clip_rows / _flow_clip_replay) also the deque motion_data and _flow_n, the number of points the
-tracking session still has.
+tracking session still has.  For the 'phase' method's clips (_phase_clip_rows / _phase_clip_replay) the deque motion_data.
 """
 import numpy as np
 
@@ -93,5 +93,36 @@ class BreathSignal:
             self.motion_data.append([mean[i][0], mean[i][1]])               # base.py:389
             if len(self.motion_data) >= 2:
                 return float(pca[i])                                        # base.py:396-405
+            return 0.0
+        return value
+
+    # ------------------------------------------------------------------ a clip of extract_motion('phase')
+    # sums [N,3]: Sw, Sc, Ss of every frame (rm_phase_motion_clip).  A frame yields the 2-vector v = (Sc / Sw, Ss / Sw), the mean phase
+    # velocity, where the flow path's frame yields its mean flow; behind that the bookkeeping is the flow path's.  `begins`: the clip's
+    # first frame is the session's first (zeros; it only becomes the state).
+    def _phase_clip_rows(self, sums, begins):
+        """(rows, first): motion_data followed by the rows the clip appends to it -- one per frame with Sw > 0 -- and the index of the
+        first new row; frame i's PCA runs over the measure_buffer_length rows ending in its own (see _flow_clip_rows)."""
+        new = [[s[1] / s[0], s[2] / s[0]] for i, s in enumerate(sums) if not (begins and i == 0) and s[0] > 0]
+        first = len(self.motion_data)
+        rows = np.array(list(self.motion_data) + new, dtype=np.float32).reshape(-1, 2)
+        return rows, first
+
+    def _phase_clip_replay(self, sums, begins, pca):
+        """value(i) = what extract_motion() returns for frame i of the clip: pca holds the values of its new rows.  To be called once
+        per frame, in order, behind the popleft rule."""
+        taken = [0]
+
+        def value(i):
+            if begins and i == 0:
+                return 0.0
+            Sw, Sc, Ss = sums[i]
+            if not Sw > 0:
+                return np.nan                                               # (the object np.nan: detect_errors tests identity)
+            self.motion_data.append([np.float32(Sc / Sw), np.float32(Ss / Sw)])
+            j = taken[0]
+            taken[0] += 1
+            if len(self.motion_data) >= 2:
+                return float(pca[j])
             return 0.0
         return value

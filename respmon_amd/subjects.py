@@ -21,6 +21,13 @@ rm_pca_reduce_windows_multi call for all of them.  Subject k then equals a Respi
 'measure' state after skip_calibration(*roi_k), up to and including the frame on which that monitor would leave 'measure' ("No
 motion key points found.", or a NaN value once the last point is lost): there the subject is marked `lost` and ignored until
 SubjectTracker.restart(k) begins its tracking again.
+
+    tracker = SubjectTracker(rois, fps, motion_extraction_method='phase', phase_params=dict(level=1))
+
+measures the amplitude-weighted mean phase velocity of one Riesz-pyramid level of every region (the method for regions that move a
+fraction of a pixel at constant brightness and offer texture, not corners): ONE rm_phase_motion_multi_clip call and ONE
+rm_pca_reduce_windows_multi call per clip, every subject on a session of its own, subject k equal to a
+RespiratoryMonitor(motion_extraction_method='phase') after skip_calibration(*roi_k) in the same sense.
 """
 from collections import deque
 
@@ -34,7 +41,7 @@ class Subject(BreathSignal):
     RespiratoryMonitor (hyperparameters: base.py:80-106)."""
 
     def __init__(self, roi, fps, freq_max=1.0, measure_buffer_length=128, measure_initialization_length=12, filter_order=3,
-                 gaussian_cutoff=10.0, save_all_data=False, flow_state=None):
+                 gaussian_cutoff=10.0, save_all_data=False, flow_state=None, phase_state=None):
         self.x, self.y, self.w, self.h = (int(v) for v in roi)
         self.fps = fps
         self.freq_max = freq_max
@@ -54,6 +61,11 @@ class Subject(BreathSignal):
             self._flow_state, self._flow_begun, self._flow_n = flow_state, False, 0
             self.motion_data = deque()
             self.buffers.append(self.motion_data)                           # base.py:473-475 reaches it as in the reference
+            self.disable_error_detection = False
+        if phase_state is not None:             # 'phase': one session (rm_phase_motion) and the list of mean phase velocities
+            self._phase_state, self._phase_begun = phase_state, False
+            self.motion_data = deque()
+            self.buffers.append(self.motion_data)
             self.disable_error_detection = False
 
     def detect_errors(self):
@@ -78,14 +90,16 @@ class Subject(BreathSignal):
 class SubjectTracker:
     def __init__(self, rois, fps, freq_max=1.0, measure_buffer_length=128, measure_initialization_length=12, filter_order=3,
                  gaussian_cutoff=10.0, save_all_data=False, backend=None, motion_extraction_method='average', feature_params=None,
-                 lk_params=None):
+                 lk_params=None, phase_params=None):
         """rois: a sequence of (x, y, w, h), e.g. what RespiratoryMonitor.locate_all returned (1 .. RM_MAX_ROIS = 64 of them);
         fps: frames per second of the clips; the other arguments are the monitor's hyperparameters of the same names.
-        motion_extraction_method: 'average' (the region means) or 'flow' (optical flow + PCA); feature_params / lk_params: the
-        arguments of goodFeaturesToTrack / calcOpticalFlowPyrLK in 'flow' mode, by default the monitor's (base.py:91-98).
+        motion_extraction_method: 'average' (the region means), 'flow' (optical flow + PCA) or 'phase' (mean phase velocity + PCA);
+        feature_params / lk_params: the arguments of goodFeaturesToTrack / calcOpticalFlowPyrLK in 'flow' mode, by default the monitor's
+        (base.py:91-98); phase_params: dict(level=1), the pyramid level of the 'phase' mode.
         backend -- a stand-in for the device backend (tests): an object with roi_mean_multi_clip(frames, rois) -> ndarray [N, K],
-        in 'flow' mode with flow_state / flow_begin / flow_points / flow_multi_clip / pca_reduce_windows_multi of _Backend."""
-        assert motion_extraction_method in ("average", "flow"), "motion_extraction_method must be 'average' or 'flow'"
+        in 'flow' mode with flow_state / flow_begin / flow_points / flow_multi_clip / pca_reduce_windows_multi of _Backend, in 'phase'
+        mode with phase_motion_state / phase_motion_multi_clip / pca_reduce_windows_multi."""
+        assert motion_extraction_method in ("average", "flow", "phase"), "motion_extraction_method must be 'average', 'flow' or 'phase'"
         rois = [tuple(int(v) for v in r) for r in rois]
         if not rois:
             raise ValueError("SubjectTracker needs at least one region")
@@ -96,9 +110,12 @@ class SubjectTracker:
         self.motion_extraction_method = motion_extraction_method
         self.feature_params = dict(feature_params) if feature_params else dict(maxCorners=100, qualityLevel=0.3, minDistance=7, blockSize=7)
         self.lk_params = dict(lk_params) if lk_params else dict(winSize=(15, 15), maxLevel=2, criteria=(3, 10, 0.03))
-        flow = motion_extraction_method == "flow"
+        self.phase_params = dict(level=1)
+        self.phase_params.update(phase_params or {})
+        flow, phase = motion_extraction_method == "flow", motion_extraction_method == "phase"
         self.subjects = [Subject(r, fps, freq_max, measure_buffer_length, measure_initialization_length, filter_order, gaussian_cutoff,
-                                 save_all_data, flow_state=backend.flow_state() if flow else None) for r in rois]
+                                 save_all_data, flow_state=backend.flow_state() if flow else None,
+                                 phase_state=self._phase_state(r) if phase else None) for r in rois]
         self._rois = np.array(rois, dtype=np.int32).reshape(-1, 4)
 
     @property
@@ -131,10 +148,10 @@ class SubjectTracker:
         if isinstance(frames, np.ndarray) and isinstance(self._backend, _Backend):
             from . import device
             frames = device.to_device(frames)
-        if self.motion_extraction_method == "flow":
+        if self.motion_extraction_method in ("flow", "phase"):
             live = [k for k, s in enumerate(self.subjects) if not s.lost]
             if live:
-                self._flow_clip(frames, live)
+                (self._flow_clip if self.motion_extraction_method == "flow" else self._phase_clip)(frames, live)
             return len(frames)
         means = self._backend.roi_mean_multi_clip(frames, self._rois)
         n = len(means)
@@ -158,6 +175,8 @@ class SubjectTracker:
         s.lost, s.error_message = False, None
         if self.motion_extraction_method == "flow":
             s._flow_begun, s._flow_n = False, 0
+        if self.motion_extraction_method == "phase":   # a new session: the rectangle may have another size
+            s._phase_state, s._phase_begun = self._phase_state(s.roi), False
 
     def motion_key_points(self, k):
         """The points subject k still tracks ('flow' mode), [n,1,2] float32 in the ROI's coordinates as rm_flow_points returns them;
@@ -202,6 +221,36 @@ class SubjectTracker:
             pca = [[] for _ in subs]
         for j, s in enumerate(subs):
             value_of = s._flow_clip_replay(mean[:, j], n_good[:, j], pca[j]) if tracked[j] else (lambda i: np.nan)
+            for i in range(len(frames)):
+                s._pop_full_buffers()                                       # base.py:473-475
+                s._record_value(value_of(i))                                # base.py:477-497
+                if s.lost:
+                    break                                                   # later frames are ignored for this subject
+
+    # ---- 'phase' mode ----------------------------------------------------------------------------------------------------------
+    def _phase_state(self, roi):
+        return self._backend.phase_motion_state(int(roi[2]), int(roi[3]), int(self.phase_params["level"]))
+
+    def _phase_clip(self, frames, ks):
+        """The frames of a clip for the subjects `ks` (none of them lost): RespiratoryMonitor._phase_clip_values for all of them at once."""
+        be = self._backend
+        if len(frames) == 0 or not ks:
+            return
+        subs = [self.subjects[k] for k in ks]
+        sums = be.phase_motion_multi_clip([s._phase_state for s in subs], frames, self._rois[ks])
+        begins = [not s._phase_begun for s in subs]
+        rows, firsts = [], []
+        for j, s in enumerate(subs):
+            s._phase_begun = True
+            r, first = s._phase_clip_rows(sums[:, j], begins[j])
+            rows.append(r)
+            firsts.append(first)
+        if any(len(r) > f for r, f in zip(rows, firsts)):
+            pca = be.pca_reduce_windows_multi(rows, firsts, subs[0].measure_buffer_length)
+        else:
+            pca = [[] for _ in subs]
+        for j, s in enumerate(subs):
+            value_of = s._phase_clip_replay(sums[:, j], begins[j], pca[j])
             for i in range(len(frames)):
                 s._pop_full_buffers()                                       # base.py:473-475
                 s._record_value(value_of(i))                                # base.py:477-497

@@ -20,10 +20,11 @@ DEFAULT = os.path.join(ROOT, "respmon_amd", "csrc", "build_resources.txt")
 #     SYM = 0 instances of k_magnify (one frame tile in flight) fall under the k_magnify pattern with the SYM = 1 ones
 # ... and phase-based magnification (rm_phase.hip): k_phase_time keeps 5 + 4 nsec state values of its pixel in registers over a whole push,
 #     k_phase_space streams three planes per frame
+# ... and the 'phase' motion signal (rm_phase_motion.hip): k_pm_reduce keeps the previous frame's I, R1, R2, A of its pixel in registers over a chunk
 # ... and the multi-subject ROI mean (rm_subjects.h): a workgroup per (frame, subject) pair streams its rectangle once
 MUST_NOT_SPILL = re.compile(r"^(void )?rm::k_down_chain<[^>]*, false>|^(void )?rm::k_down_chain_stitch<|^(void )?rm::k_down_chain_u8<|^(void )?rm::k_down_chain_narrow<|"
                             r"^(void )?rm::k_magnify<|^(void )?rm::k_roi_mean_multi_clip<|"
-                            r"^(void )?rm::k_lk_track_multi_clip<|^(void )?rm::k_sosfilt<|^(void )?rm::k_phase_time<|^(void )?rm::k_phase_space<")
+                            r"^(void )?rm::k_lk_track_multi_clip<|^(void )?rm::k_sosfilt<|^(void )?rm::k_phase_time<|^(void )?rm::k_phase_space<|^(void )?rm::k_pm_reduce\b")
 # kernels (mangled names, as the report spells them) that may be compiled in more than one unit, each with its reason.  None: wherever
 # several units need a kernel, one of them holds a launcher for it (launch_state_init, threshold_mask, launch_heat_minmax, ...).
 MAY_REPEAT = set()
