@@ -567,6 +567,68 @@ int rm_phase_motion_clip(rm_ctx *ctx, rm_phase_motion *st, const void *frames_de
 int rm_phase_motion_multi_clip(rm_ctx *ctx, rm_phase_motion *const *states_host /* [K] */, const void *frames_dev, int dtype, int N, int H, int W,
                                const int32_t *rois_host /* [K][4] x,y,w,h */, int K, double *sums_host /* [N][K][3] */, void *stream);
 
+/* ---- rm_stab_*, rm_warp_shift: a shaky camera taken out of the frames (no counterpart in the reference: every method there and here
+ *      assumes a camera that stands still).  Per frame the global shift against a fixed reference frame, and the warp by it.
+ *      THE ORDER OF OPERATIONS IS PART OF THE INTERFACE.  Everything is float64, every operation rounds once (-ffp-contract=off).
+ *
+ *      Session.  rm_stab belongs to one frame size (H, W).  level_coarse >= level_fine >= 0, both <= 8; iterations >= 1; max_shift > 0
+ *        in level-0 pixels, at most 64.  The reference frame is the first frame after create or reset, or the frame given to
+ *        rm_stab_set_reference; it stays fixed for the session and shifts are relative to it, so a frame's result does not depend on
+ *        the other frames of a call, nor on how a sequence is cut into calls.
+ *      Gray value f of a frame, as the pyramid entry points convert it: RM_U8 k * (1./255), RM_U16 k * (1./65535), RM_F16 / RM_F32
+ *        widened, RM_F64 as it is, RM_BGR8 the integer cvtColor of rm_bgr_to_gray, then * (1./255).
+ *      Pyramid.  G_0 = f, G_l+1 = pyrDown(G_l) (rm_pyr_down).  R_l, F_l: the levels of the reference and of the frame, h_l x w_l.
+ *      Estimate.  d = (0, 0).  For l = level_coarse down to level_fine:
+ *          b = ceil(max_shift / 2^l) + 2; Omega = the pixels at least b from every edge (b <= x <= w_l - 1 - b, the same in y).
+ *          Omega empty: the level is skipped, flag bit 0.
+ *          Rx = 0.5 * (R[y][x+1] - R[y][x-1]), Ry = 0.5 * (R[y+1][x] - R[y-1][x]);
+ *          over Omega: a = sum Rx * Rx, bb = sum Rx * Ry, c = sum Ry * Ry; det = a * c - bb * bb.
+ *          det not finite or not > 0: the level is skipped, flag bit 0.
+ *          s = d / 2^l (exact).  `iterations` times:
+ *              e = bilinear(F_l, x + s.x, y + s.y) - R[y][x] over Omega; gx = sum Rx * e, gy = sum Ry * e;
+ *              s.x = s.x - (c * gx - bb * gy) / det; s.y = s.y - (a * gy - bb * gx) / det;
+ *              each component clamped to +- max_shift / 2^l.
+ *          d = s * 2^l.
+ *        Flag bit 1: the clamp changed a component in the last iteration of level_fine -- the frame has probably moved further than
+ *        max_shift.  d is the displacement of the frame's content against the reference, positive toward +x / +y.  The iteration count
+ *        is fixed; nothing terminates on data.
+ *      bilinear(F, fx, fy): x0 = floor(fx), ax = fx - x0, likewise y; i0 = clamp(x0, 0, w-1), i1 = clamp(x0 + 1, 0, w-1), j0, j1
+ *        likewise; ((1-ax) * F[j0][i0] + ax * F[j0][i1]) * (1-ay) + ((1-ax) * F[j1][i0] + ax * F[j1][i1]) * ay.
+ *      Order of the five sums: the implementation's, a function of (h_l, w_l, b) alone -- never of N, of the chunking or of the
+ *        frame's position in a call.  (Here: 64 x 16 tiles of the level, a lane four rows of one column top down, the 64 lanes of a
+ *        wave on DPP, the four waves in order; then one wave over the tiles, lane k tiles k, k + 64, ..., and its lanes on DPP.)  No
+ *        floating-point atomics.
+ *      Warp.  out[y][x] = bilinear(f, x + d.x, y + d.y) on the full-resolution frame, converted to out_dtype by rm_magnify's output
+ *        rules: RM_F64 as it is, RM_F32 rounded to nearest, RM_U8 / RM_U16 clamped to [0, 1], then the C truncation of * 255 / * 65535.
+ *        RM_BGR8 frames are warped channel by channel, k * (1./255) per channel, and go out as RM_BGR8 only; gray in means gray out.
+ *        So a zero shift returns the frame through its conversion rule, and an integer shift is an exact translation with a
+ *        replicated border.
+ *
+ *      rm_stab_create: the state holds R_l for l = level_fine .. level_coarse and (a, bb, c, det) per level, its own allocation on the
+ *        context's device (rm_stab_info: frames seen, whether a reference is set, bytes).
+ *      rm_stab_set_reference: the frame [H,W] (or [H,W,3] RM_BGR8) becomes the reference; asynchronous.
+ *      rm_stab_push: N >= 1 frames resident on the device -> shifts_host[N][2] (d.x, d.y), flags_host[N], and, unless out_dev is NULL
+ *        (estimate only), the N warped frames.  With no reference set the first frame becomes the reference and comes back with shift
+ *        (0, 0).  The frames' pyramids live in the context's workspace; long clips are chunked internally under a cap of 256 MiB.  The
+ *        launches of a chunk grow with the levels and iterations, never with N; the 2 x 2 update is done on the device; a call makes
+ *        one result copy and one stream wait.  RM_E_BUSY as for rm_stream_push.
+ *      rm_warp_shift: the warp alone with the caller's shifts; no session, asynchronous.  Shifts must be finite and at most 2^20 in
+ *        magnitude.
+ *      Refusal is all or nothing -- nothing is enqueued, nothing is written.  RM_E_BADARG: NULL pointers, sizes < 1, levels out of order
+ *        or negative, iterations < 1, a max_shift that is not finite or not > 0, an out dtype outside the rule, out_dev overlapping the
+ *        frames, a state of another device, a shift rm_warp_shift does not take.  RM_E_UNSUPPORTED: a level > 8, max_shift > 64.
+ *      Out of scope: rotation, zoom, rolling shutter, a drifting reference, a smoothed camera path, cropping the replicated border. */
+typedef struct rm_stab rm_stab;
+int rm_stab_create(rm_ctx *ctx, int H, int W, int level_coarse, int level_fine, int iterations, double max_shift, rm_stab **out);
+int rm_stab_destroy(rm_stab *st);
+int rm_stab_reset(rm_ctx *ctx, rm_stab *st);
+int rm_stab_info(const rm_stab *st, long long *frames_seen, int *has_reference, size_t *state_bytes);
+int rm_stab_set_reference(rm_ctx *ctx, rm_stab *st, const void *frame_dev, int dtype, void *stream);
+int rm_stab_push(rm_ctx *ctx, rm_stab *st, const void *frames_dev, int dtype, int N, void *out_dev /* nullable */, int out_dtype,
+                 double *shifts_host /* [N][2] */, int32_t *flags_host /* [N] */, void *stream);
+int rm_warp_shift(rm_ctx *ctx, const void *frames_dev, int dtype, int N, int H, int W, const double *shifts_host /* [N][2] */, void *out_dev,
+                  int out_dtype, void *stream);
+
 /* ---- base.py:355-358 + 471: extract_motion('average') = np.average(frame[y:y+h, x:x+w]) -- */
 int rm_roi_mean(rm_ctx *ctx, const void *frame_dev, int dtype, int H, int W, int x, int y, int w, int h,
                 double *out_host, void *stream);

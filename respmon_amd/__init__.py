@@ -13,7 +13,7 @@ def __getattr__(name):
     if name == "SubjectTracker":
         from .subjects import SubjectTracker
         return SubjectTracker
-    if name in ("transforms", "pyramid", "base", "device", "synth", "dist", "subjects", "measure", "live", "window"):
+    if name in ("transforms", "pyramid", "base", "device", "synth", "dist", "subjects", "measure", "live", "window", "stabilize"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

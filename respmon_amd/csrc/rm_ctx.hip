@@ -154,6 +154,7 @@ extern "C" int rm_debug_set(rm_ctx *ctx, const char *key, long long value)
     else if (k == "flow_clip_bytes") d.flow_clip_bytes = value;
     else if (k == "stream_frames") d.stream_frames = (int)value;
     else if (k == "phase_motion_frames") d.phase_motion_frames = (int)value;
+    else if (k == "stab_frames") d.stab_frames = (int)value;
     else return fail(RM_E_BADARG, "rm_debug_set: unknown key '%s'", key);
     return RM_OK;
 }

@@ -19,6 +19,7 @@
 //   rm_rate.hip           rm_spectral_peak, rm_rate_map: dominant in-band frequency per pixel column    (prototypes/temporal_analysis.py; rm_rate_kernels.h)
 //   rm_phase.hip          rm_phase_*: phase-based magnification on the Riesz pyramid, a stream object with carried state (rm_phase_kernels.h)
 //   rm_phase_motion.hip   rm_phase_motion_*: the 'phase' motion signal of extract_motion, K subjects and a clip per call (rm_phase_motion_kernels.h)
+//   rm_stabilize.hip      rm_stab_*, rm_warp_shift: the global shift of a frame against a reference frame and the warp that takes it out (rm_stabilize_kernels.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
 // A kernel is compiled in the ONE unit that launches it.  This header therefore includes no kernel header beyond what its own
 // declarations need (rm_kernels.h: the geometry structs, CollapseState, SumPlan; rm_flow_ws.h: rm_ctx embeds a FlowWorkspace) and what
@@ -138,6 +139,7 @@ struct DebugKnobs {
     long long store_slots = 0;    // > 0: capacity of the value store in (tile, frame) slots (forces the overflow path)
     int stream_frames = 0;        // > 0: frames per internal chunk of rm_stream_push and rm_phase_push (default: by the workspace cap, at most 256)
     int phase_motion_frames = 0;  // > 0: frames per internal chunk of rm_phase_motion_clip / rm_phase_motion_multi_clip at most (default: by the 256 MiB workspace cap)
+    int stab_frames = 0;          // > 0: frames per internal chunk of rm_stab_push at most (default: by the 256 MiB workspace cap)
     long long flow_clip_bytes = 0;   // > 0: workspace cap of one chunk of rm_flow_clip / rm_flow_multi_clip (default 256 MiB): a chunk holds max(1, cap / slot - 1) frames, slot = 5 bytes per pixel of every LK pyramid level of the ROI (summed over the subjects that still have points)
 };
 

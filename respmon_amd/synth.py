@@ -195,6 +195,35 @@ def synth_texture(H, W, seed=4321, n_waves=12, n_spots=40):
     return render
 
 
+def synth_shaky_breathing(T, H, W, jitter, seed=7, fps=10.0, breath_hz=0.4, amplitude=0.04, noise=0.02, center=(0.6, 0.4),
+                          sigma=(0.10, 0.08)):
+    """A breathing subject seen by a camera that shakes: synth_texture(H, W, seed) plus a Gaussian blob whose brightness oscillates at
+    `breath_hz` plus white pixel noise, the whole scene (texture and blob) displaced per frame by a shift drawn uniformly from
+    +-`jitter` pixels in x and y.  The first frame is not displaced: it is the frame a stabiliser registers the others to.
+    Returns (still, shaken, shifts): the uint8 [T,H,W] clip of the camera at rest, the clip of the shaking camera with the same
+    breathing and the same noise, and the true shifts [T,2] (dx, dy) of the scene content, positive toward +x / +y."""
+    rng = np.random.Generator(np.random.PCG64([seed, 0x5ab1]))
+    render = synth_texture(H, W, seed=seed)
+    shifts = rng.uniform(-jitter, jitter, size=(T, 2))
+    shifts[0] = 0.0
+    s = np.sin(2 * np.pi * breath_hz * np.arange(T) / fps)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+
+    def blob(dx, dy):
+        y = (yy - dy - center[0] * H) / (sigma[0] * H)
+        x = (xx - dx - center[1] * W) / (sigma[1] * W)
+        return amplitude * np.exp(-0.5 * (y * y + x * x))
+
+    still, shaken = np.empty((T, H, W), np.uint8), np.empty((T, H, W), np.uint8)
+    base0, blob0 = render(0.0, 0.0) / 255.0, blob(0.0, 0.0)
+    for t in range(T):
+        n = noise * rng.standard_normal((H, W))
+        still[t] = np.clip(np.rint(255 * (base0 + blob0 * s[t] + n)), 0, 255).astype(np.uint8)
+        dx, dy = shifts[t]
+        shaken[t] = np.clip(np.rint(255 * (render(dx, dy) / 255.0 + blob(dx, dy) * s[t] + n)), 0, 255).astype(np.uint8)
+    return still, shaken, shifts
+
+
 class FakeCapture:
     """Stands in for cv2.VideoCapture (reference base.py:48-51, 227-233).
     frames: uint8 [T,H,W,3] BGR (or [T,H,W] gray, returned as 3 equal channels); uint16 [T,H,W] frames are returned as they are, 2-D,

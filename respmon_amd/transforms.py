@@ -347,6 +347,15 @@ def phase_magnification_video(vid_data, fps, freq_min, freq_max, amplification, 
         return device.like_input(pm.push(vid), vid_data)
 
 
+def stabilize_video(vid_data, out_dtype=None, return_shifts=False, **kw):
+    """A clip of a shaky camera registered to its first frame (rm_stab_* of include/respmon_hip.h): one stabilize.Stabilizer(H, W,
+    **kw), one push -- per frame the global shift against the first frame, then the bilinear warp by it.  `vid_data`: [T,H,W] gray or
+    [T,H,W,3] uint8 BGR; numpy in -> numpy out, device tensor in -> device tensor out; **kw: max_shift, levels, iterations.
+    return_shifts=True: (frames, shifts [T,2], flags [T])."""
+    from .stabilize import stabilize_video as _stabilize_video
+    return _stabilize_video(vid_data, out_dtype=out_dtype, return_shifts=return_shifts, **kw)
+
+
 def butter_lowpass_filter(data, cutoff, fs, order=5):
     """reference transforms.py:58-69 (used by measure(), base.py:342): 128-sample 1-D signal, host scipy."""
     from scipy.signal import butter, filtfilt
