@@ -629,6 +629,69 @@ int rm_stab_push(rm_ctx *ctx, rm_stab *st, const void *frames_dev, int dtype, in
 int rm_warp_shift(rm_ctx *ctx, const void *frames_dev, int dtype, int N, int H, int W, const double *shifts_host /* [N][2] */, void *out_dev,
                   int out_dtype, void *stream);
 
+/* ---- rm_stab_sim_*, rm_warp_similarity: a hand-held camera taken out of the frames -- rotation about the optical axis, zoom and
+ *      shift, a second model beside rm_stab, which stays as it is.  One degree of roll moves the corners of a 1080p frame by 19 px.
+ *      THE ORDER OF OPERATIONS IS PART OF THE INTERFACE.  Everything is float64, every operation rounds once (-ffp-contract=off).
+ *
+ *      Session.  rm_stab_sim belongs to one frame size (H, W).  level_coarse >= level_fine >= 0, both <= 8; level_linear in
+ *        -1 .. level_coarse; iterations >= 1; max_shift in (0, 64] level-0 pixels; max_linear in (0, 0.25].  The reference frame, the
+ *        gray value f, the pyramid G_l and bilinear() are rm_stab's.
+ *      Transform.  p = (p0, p1, tx, ty), p0 = s cos(theta) - 1, p1 = s sin(theta): a similarity is linear in p.  With
+ *        cx = (W - 1) * 0.5, cy = (H - 1) * 0.5, u = x - cx, v = y - cy, m = 1 + p0:
+ *            fx = (cx + (m * u - p1 * v)) + tx;  fy = (cy + (p1 * u + m * v)) + ty
+ *        is the position in the frame of reference pixel (x, y).  At level l, inv = 1 / 2^l (exact): the same formula with cx * inv,
+ *        cy * inv, (tx, ty) * inv and level-pixel coordinates; p0 and p1 do not scale.
+ *      Estimate.  p = 0.  For l = level_coarse down to level_fine:
+ *        l > level_linear: the level step of rm_stab, unchanged -- its b, its five sums, its 2 x 2 update and its clamp on (tx, ty);
+ *          p0 = p1 = 0 still holds there, so the sample positions are rm_stab's bit for bit.
+ *        l <= level_linear:
+ *          b = ceil((max_shift + max_linear * (cx + cy)) * inv) + 2 (cx, cy of level 0); Omega, Rx, Ry as in rm_stab; Omega empty: the
+ *            level is skipped, flag bit 0.
+ *          J0 = Rx * u + Ry * v, J1 = Ry * u - Rx * v, J2 = Rx, J3 = Ry (u, v in level pixels against cx * inv, cy * inv).
+ *          H_ij = sum over Omega of J_i * J_j for i >= j: ten sums, once per reference and level.
+ *          H = L D L^T, row by row, no square root:
+ *            D_j = H_jj - sum_{k<j} (L_jk * L_jk) * D_k;  L_ij = (H_ij - sum_{k<j} (L_ik * L_jk) * D_k) / D_j,
+ *            each inner sum left to right (D_0 = H_00, L_i0 = H_i0 / D_0).
+ *          A D_j not finite or not > 0: the level is skipped, flag bit 0.
+ *          s = (tx, ty) * inv.  `iterations` times:
+ *            e = bilinear(F_l, fx, fy) - R[y][x] over Omega; g_i = sum (J_i) * e (J_i formed as above, then one product);
+ *            L z = g:    z0 = g0; z1 = g1 - L10 * z0; z2 = g2 - (L20 * z0 + L21 * z1); z3 = g3 - ((L30 * z0 + L31 * z1) + L32 * z2);
+ *            y_i = z_i / D_i;
+ *            L^T x = y:  x3 = y3; x2 = y2 - L32 * x3; x1 = y1 - (L21 * x2 + L31 * x3); x0 = y0 - ((L10 * x1 + L20 * x2) + L30 * x3);
+ *            p0 = p0 - x0; p1 = p1 - x1; s.x = s.x - x2; s.y = s.y - x3;
+ *            p0, p1 clamped to +- max_linear; s.x, s.y clamped to +- max_shift * inv.
+ *          (tx, ty) = s * 2^l.
+ *        Flags.  Bit 0: a level was skipped.  Bit 1: the shift clamp changed a component in the last iteration of level_fine, as in
+ *        rm_stab.  Bit 2: the linear clamp did.
+ *        level_linear exists because the region of a very coarse level is a few pixels, and four parameters are not determined there:
+ *        keep it at 1 or 2.  level_linear < level_fine estimates no linear part, and the session then is rm_stab: (0, 0, d).
+ *      Order of the sums: the implementation's, a function of (h_l, w_l, b) alone, as in rm_stab -- the same 64 x 16 tiles, DPP fold,
+ *        wave order and one-wave fold over the tiles.  No floating-point atomics.
+ *      Warp.  out[y][x] = bilinear(f, fx, fy) with the level-0 formula, converted by rm_magnify's output rules; RM_BGR8 channel by
+ *        channel, out as RM_BGR8 only; gray in means gray out.  With p0 = p1 = 0 the position is x + tx exactly: rm_warp_shift.
+ *
+ *      rm_stab_sim_create / _destroy / _reset / _info / _set_reference: as rm_stab's.  The state holds R_l and, per level, (a, bb, c,
+ *        det) or the factors L, D and a validity word.
+ *      rm_stab_sim_push: N >= 1 frames resident on the device -> params_host[N][4] (p0, p1, tx, ty), flags_host[N] and, unless out_dev
+ *        is NULL, the warped frames.  Chunked under the 256 MiB workspace cap; the launches of a chunk do not grow with N; the update is
+ *        done on the device; one result copy and one stream wait per call.  RM_E_BUSY as for rm_stream_push.
+ *      rm_warp_similarity: the warp alone with the caller's parameters; no session, asynchronous.
+ *      Refusal is all or nothing.  RM_E_BADARG: what rm_stab refuses, a level_linear outside -1 .. level_coarse, a max_linear that is not
+ *        finite or not > 0, and in rm_warp_similarity parameters that are not finite, |p0| or |p1| > 1, |tx| or |ty| > 2^20.
+ *        RM_E_UNSUPPORTED: a level > 8, max_shift > 64, max_linear > 0.25.
+ *      Out of scope: shear, perspective, rolling shutter, a camera that pans on purpose, a drifting reference. */
+typedef struct rm_stab_sim rm_stab_sim;
+int rm_stab_sim_create(rm_ctx *ctx, int H, int W, int level_coarse, int level_fine, int level_linear, int iterations, double max_shift,
+                       double max_linear, rm_stab_sim **out);
+int rm_stab_sim_destroy(rm_stab_sim *st);
+int rm_stab_sim_reset(rm_ctx *ctx, rm_stab_sim *st);
+int rm_stab_sim_info(const rm_stab_sim *st, long long *frames_seen, int *has_reference, size_t *state_bytes);
+int rm_stab_sim_set_reference(rm_ctx *ctx, rm_stab_sim *st, const void *frame_dev, int dtype, void *stream);
+int rm_stab_sim_push(rm_ctx *ctx, rm_stab_sim *st, const void *frames_dev, int dtype, int N, void *out_dev /* nullable */, int out_dtype,
+                     double *params_host /* [N][4] */, int32_t *flags_host /* [N] */, void *stream);
+int rm_warp_similarity(rm_ctx *ctx, const void *frames_dev, int dtype, int N, int H, int W, const double *params_host /* [N][4] */, void *out_dev,
+                       int out_dtype, void *stream);
+
 /* ---- base.py:355-358 + 471: extract_motion('average') = np.average(frame[y:y+h, x:x+w]) -- */
 int rm_roi_mean(rm_ctx *ctx, const void *frame_dev, int dtype, int H, int W, int x, int y, int w, int h,
                 double *out_host, void *stream);

@@ -30,8 +30,8 @@ extern "C" {
  * reaches the split with a handful of frames.
  * "phase_motion_frames" n: frames per internal chunk of rm_phase_motion_clip and rm_phase_motion_multi_clip at most (0: by their 256 MiB
  * workspace cap), so that a test reaches the split -- and the alternation of the state's two planes -- with a handful of frames.
- * "stab_frames" n: frames per internal chunk of rm_stab_push at most (0: by its 256 MiB workspace cap), so that a test reaches the split
- * with a handful of frames.
+ * "stab_frames" n: frames per internal chunk of rm_stab_push and rm_stab_sim_push at most (0: by their 256 MiB workspace cap), so that a
+ * test reaches the split with a handful of frames.
  * "rate_wide" 0|1: the K-split / the wave-per-16-columns form of the rate map's kernel whatever the level size (-1: by size). */
 int rm_debug_set(rm_ctx *ctx, const char *key, long long value);
 

@@ -127,6 +127,13 @@ SIGNATURES = {
     "rm_stab_set_reference": (_i, [_vp, _vp, _vp, _i, _vp]),
     "rm_stab_push": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "rm_warp_shift": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "rm_stab_sim_create": (_i, [_vp, _i, _i, _i, _i, _i, _i, _d, _d, _c.POINTER(_vp)]),
+    "rm_stab_sim_destroy": (_i, [_vp]),
+    "rm_stab_sim_reset": (_i, [_vp, _vp]),
+    "rm_stab_sim_info": (_i, [_vp, _c.POINTER(_c.c_longlong), _c.POINTER(_i), _c.POINTER(_sz)]),
+    "rm_stab_sim_set_reference": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "rm_stab_sim_push": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "rm_warp_similarity": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "rm_roi_mean": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_roi_to_uint8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "rm_good_features_to_track": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp]),

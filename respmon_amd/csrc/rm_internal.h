@@ -19,7 +19,8 @@
 //   rm_rate.hip           rm_spectral_peak, rm_rate_map: dominant in-band frequency per pixel column    (prototypes/temporal_analysis.py; rm_rate_kernels.h)
 //   rm_phase.hip          rm_phase_*: phase-based magnification on the Riesz pyramid, a stream object with carried state (rm_phase_kernels.h)
 //   rm_phase_motion.hip   rm_phase_motion_*: the 'phase' motion signal of extract_motion, K subjects and a clip per call (rm_phase_motion_kernels.h)
-//   rm_stabilize.hip      rm_stab_*, rm_warp_shift: the global shift of a frame against a reference frame and the warp that takes it out (rm_stabilize_kernels.h)
+//   rm_stabilize.hip      rm_stab_*, rm_warp_shift: the global shift of a frame against a reference frame and the warp that takes it out;
+//                         rm_stab_sim_*, rm_warp_similarity: the same for rotation, zoom and shift (rm_stabilize_kernels.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
 // A kernel is compiled in the ONE unit that launches it.  This header therefore includes no kernel header beyond what its own
 // declarations need (rm_kernels.h: the geometry structs, CollapseState, SumPlan; rm_flow_ws.h: rm_ctx embeds a FlowWorkspace) and what

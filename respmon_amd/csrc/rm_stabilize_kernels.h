@@ -235,4 +235,180 @@ __global__ __launch_bounds__(256) void k_stab_warp_bgr(const uint8_t *frames, in
     for (int y = (int)blockIdx.y; y < H; y += (int)gridDim.y) o[(size_t)y * 3 * W + e] = mag_out<uint8_t>(stab_bilinear(F, H, W, fx, (double)y + dy));
 }
 
+// ---- rm_stab_sim_*, rm_warp_similarity: the similarity model (rotation, zoom, shift) beside the shift model above.  Parameters
+// p = (p0, p1, tx, ty), p0 = s cos(theta) - 1, p1 = s sin(theta); between the launches the shift d = (tx, ty) [n][2] and the linear part
+// q = (p0, p1) [n][2] are kept apart, so that the levels above level_linear run k_stab_resid / k_stab_update as they are.
+//   * k_stab_hsums_sim / k_stab_hfold_sim: the ten sums H_ij = sum J_i J_j (i >= j) of a reference level, tiled and folded as above; the
+//     one wave that folds the tiles also factors H = L D L^T and stores (L10, L20, L21, L30, L31, L32, D0 .. D3, valid) of the level.
+//   * k_stab_resid_sim: g_i = sum J_i e at the frame's present parameters; the taps are gathered (the positions form no grid), every
+//     index through stab_clamp_index.
+//   * k_stab_update_sim: one wave per frame folds the tiles, does the two substitutions, the clamps and the flags.
+//   * k_stab_pack_sim: (q, d) -> params [n][4], what the warp reads and the caller gets.
+//   * k_stab_warp_sim<Tin, Tout> / k_stab_warp_sim_bgr: out = bilinear(frame, fx, fy) at the level-0 position of the rule.
+constexpr int STAB_FLAG_LINEAR_CLAMPED = 4;
+constexpr int STAB_SIM_HDR = 16;   // doubles per level in the session's header: (a, bb, c, det) of a shift level, or L (6), D (4), valid
+
+// the position in the frame of reference pixel (c.x + u, c.y + v): fx = (cx + (m u - p1 v)) + tx, fy = (cy + (p1 u + m v)) + ty
+__device__ __forceinline__ double stab_sim_fx(double cx, double u, double v, double m, double p1, double tx) { return (cx + (m * u - p1 * v)) + tx; }
+__device__ __forceinline__ double stab_sim_fy(double cy, double u, double v, double m, double p1, double ty) { return (cy + (p1 * u + m * v)) + ty; }
+
+// grid: (tiles of the level); R: h x w; b: the border of the region; (cx, cy): the centre in level pixels; part: [ntiles][10]
+__global__ __launch_bounds__(256) void k_stab_hsums_sim(const double *R, int h, int w, int b, double cx, double cy, double *part)
+{
+    __shared__ double red[4][10];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int ntx = (w + STAB_TW - 1) / STAB_TW;
+    const int x = (int)(blockIdx.x % (unsigned)ntx) * STAB_TW + lane, y0 = (int)(blockIdx.x / (unsigned)ntx) * STAB_TH + wave * STAB_RPW;
+    double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int r = 0; r < STAB_RPW; ++r) {
+        const int y = y0 + r;
+        if (x >= b && x <= w - 1 - b && y >= b && y <= h - 1 - b) {
+            const double *p = R + (size_t)y * w + x;
+            const double Rx = 0.5 * (p[1] - p[-1]), Ry = 0.5 * (p[w] - p[-w]);
+            const double u = (double)x - cx, v = (double)y - cy;
+            const double J[4] = {Rx * u + Ry * v, Ry * u - Rx * v, Rx, Ry};
+            int k = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j <= i; ++j) s[k++] += J[i] * J[j];
+        }
+    }
+    stab_block_fold<10>(s, red, part + (size_t)blockIdx.x * 10);
+}
+
+// one wave; hs: STAB_SIM_HDR doubles of the level.  H = L D L^T row by row, no square root; every inner sum left to right
+__global__ __launch_bounds__(64) void k_stab_hfold_sim(const double *part, int ntiles, double *hs)
+{
+    double s[10];
+    stab_wave_fold<10>(part, ntiles, s);
+    if (threadIdx.x != 0) return;
+    const double H00 = s[0], H10 = s[1], H11 = s[2], H20 = s[3], H21 = s[4], H22 = s[5], H30 = s[6], H31 = s[7], H32 = s[8], H33 = s[9];
+    const double D0 = H00;
+    const double L10 = H10 / D0;
+    const double D1 = H11 - (L10 * L10) * D0;
+    const double L20 = H20 / D0;
+    const double L21 = (H21 - (L20 * L10) * D0) / D1;
+    const double D2 = H22 - ((L20 * L20) * D0 + (L21 * L21) * D1);
+    const double L30 = H30 / D0;
+    const double L31 = (H31 - (L30 * L10) * D0) / D1;
+    const double L32 = (H32 - ((L30 * L20) * D0 + (L31 * L21) * D1)) / D2;
+    const double D3 = H33 - (((L30 * L30) * D0 + (L31 * L31) * D1) + (L32 * L32) * D2);
+    const double big = 1.7976931348623157e308;
+    const bool ok = D0 > 0.0 && D0 <= big && D1 > 0.0 && D1 <= big && D2 > 0.0 && D2 <= big && D3 > 0.0 && D3 <= big;
+    hs[0] = L10; hs[1] = L20; hs[2] = L21; hs[3] = L30; hs[4] = L31; hs[5] = L32;
+    hs[6] = D0; hs[7] = D1; hs[8] = D2; hs[9] = D3;
+    hs[10] = ok ? 1.0 : 0.0;
+}
+
+// grid: (tiles of level l, n); inv = 1 / 2^l; d, q: [n][2], d in level-0 pixels; (cx, cy): the centre in level pixels; part: [n][ntiles][4]
+__global__ __launch_bounds__(256) void k_stab_resid_sim(StabGeom g, const double *wsp, const double *state, int l, int b, double inv, double cx, double cy,
+                                                        const double *d, const double *q, double *part)
+{
+    __shared__ double red[4][4];
+    const int h = g.h[l], w = g.w[l];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int ntx = (w + STAB_TW - 1) / STAB_TW;
+    const int x = (int)(blockIdx.x % (unsigned)ntx) * STAB_TW + lane, y0 = (int)(blockIdx.x / (unsigned)ntx) * STAB_TH + wave * STAB_RPW;
+    const double sx = d[2 * (size_t)blockIdx.y] * inv, sy = d[2 * (size_t)blockIdx.y + 1] * inv;
+    const double m = 1.0 + q[2 * (size_t)blockIdx.y], p1 = q[2 * (size_t)blockIdx.y + 1];
+    const double *R = state + g.roff[l];
+    const GlobalImg F{wsp + g.off[l] + (size_t)blockIdx.y * h * w, w};
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int r = 0; r < STAB_RPW; ++r) {
+        const int y = y0 + r;
+        if (x >= b && x <= w - 1 - b && y >= b && y <= h - 1 - b) {
+            const double *p = R + (size_t)y * w + x;
+            const double Rx = 0.5 * (p[1] - p[-1]), Ry = 0.5 * (p[w] - p[-w]);
+            const double u = (double)x - cx, v = (double)y - cy;
+            const double e = stab_bilinear(F, h, w, stab_sim_fx(cx, u, v, m, p1, sx), stab_sim_fy(cy, u, v, m, p1, sy)) - p[0];
+            s[0] += (Rx * u + Ry * v) * e; s[1] += (Ry * u - Rx * v) * e; s[2] += Rx * e; s[3] += Ry * e;
+        }
+    }
+    stab_block_fold<4>(s, red, part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4);
+}
+
+// grid: (n), one wave per frame.  hs: the level's header; lim = max_shift / 2^l; lin = max_linear; scale = 2^l, inv = 1 / 2^l
+__global__ __launch_bounds__(64) void k_stab_update_sim(const double *part, int ntiles, const double *hs, double lim, double lin, double scale, double inv,
+                                                        int last_of_fine, double *d, double *q, int32_t *flags)
+{
+    double gs[4];
+    stab_wave_fold<4>(part + (size_t)blockIdx.x * ntiles * 4, ntiles, gs);
+    if (threadIdx.x != 0) return;
+    if (!(hs[10] == 1.0)) {   // a D_j not finite or not > 0: the level is skipped
+        flags[blockIdx.x] |= STAB_FLAG_LEVEL_SKIPPED;
+        return;
+    }
+    const double L10 = hs[0], L20 = hs[1], L21 = hs[2], L30 = hs[3], L31 = hs[4], L32 = hs[5];
+    // L z = g
+    const double z0 = gs[0];
+    const double z1 = gs[1] - L10 * z0;
+    const double z2 = gs[2] - (L20 * z0 + L21 * z1);
+    const double z3 = gs[3] - ((L30 * z0 + L31 * z1) + L32 * z2);
+    // y = z / D
+    const double y0 = z0 / hs[6], y1 = z1 / hs[7], y2 = z2 / hs[8], y3 = z3 / hs[9];
+    // L^T x = y
+    const double x3 = y3;
+    const double x2 = y2 - L32 * x3;
+    const double x1 = y1 - (L21 * x2 + L31 * x3);
+    const double x0 = y0 - ((L10 * x1 + L20 * x2) + L30 * x3);
+    double p0 = q[2 * (size_t)blockIdx.x] - x0, p1 = q[2 * (size_t)blockIdx.x + 1] - x1;
+    double sx = d[2 * (size_t)blockIdx.x] * inv - x2, sy = d[2 * (size_t)blockIdx.x + 1] * inv - x3;
+    const bool lin_clamped = p0 < -lin || p0 > lin || p1 < -lin || p1 > lin;
+    const bool clamped = sx < -lim || sx > lim || sy < -lim || sy > lim;
+    p0 = p0 < -lin ? -lin : (p0 > lin ? lin : p0);
+    p1 = p1 < -lin ? -lin : (p1 > lin ? lin : p1);
+    sx = sx < -lim ? -lim : (sx > lim ? lim : sx);
+    sy = sy < -lim ? -lim : (sy > lim ? lim : sy);
+    q[2 * (size_t)blockIdx.x] = p0; q[2 * (size_t)blockIdx.x + 1] = p1;
+    d[2 * (size_t)blockIdx.x] = sx * scale; d[2 * (size_t)blockIdx.x + 1] = sy * scale;
+    if (last_of_fine && clamped) flags[blockIdx.x] |= STAB_FLAG_CLAMPED;
+    if (last_of_fine && lin_clamped) flags[blockIdx.x] |= STAB_FLAG_LINEAR_CLAMPED;
+}
+
+// params[i] = (q[i], d[i]) = (p0, p1, tx, ty)
+__global__ __launch_bounds__(64) void k_stab_pack_sim(const double *d, const double *q, double *params, int n)
+{
+    const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (i >= n) return;
+    params[4 * (size_t)i] = q[2 * i]; params[4 * (size_t)i + 1] = q[2 * i + 1];
+    params[4 * (size_t)i + 2] = d[2 * i]; params[4 * (size_t)i + 3] = d[2 * i + 1];
+}
+
+// grid and lanes as k_stab_warp.  params: [n][4]
+template <typename Tin, typename Tout>
+__global__ __launch_bounds__(256) void k_stab_warp_sim(const Tin *frames, int H, int W, const double *params, Tout *out)
+{
+    const int x = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (x >= W) return;
+    const size_t px = (size_t)H * W;
+    const StabFrame<Tin> F{frames + (size_t)blockIdx.z * px, W};
+    const double *p = params + 4 * (size_t)blockIdx.z;
+    const double cx = (double)(W - 1) * 0.5, cy = (double)(H - 1) * 0.5, m = 1.0 + p[0], p1 = p[1], tx = p[2], ty = p[3];
+    const double u = (double)x - cx;
+    Tout *o = out + (size_t)blockIdx.z * px;
+    for (int y = (int)blockIdx.y; y < H; y += (int)gridDim.y) {
+        const double v = (double)y - cy;
+        o[(size_t)y * W + x] = mag_out<Tout>(stab_bilinear(F, H, W, stab_sim_fx(cx, u, v, m, p1, tx), stab_sim_fy(cy, u, v, m, p1, ty)));
+    }
+}
+
+// the colour form: grid and lanes as k_stab_warp_bgr
+__global__ __launch_bounds__(256) void k_stab_warp_sim_bgr(const uint8_t *frames, int H, int W, const double *params, uint8_t *out)
+{
+    const int e = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (e >= 3 * W) return;
+    const int x = e / 3, ch = e - 3 * x;
+    const size_t px = (size_t)H * W;
+    const StabChannel F{frames + (size_t)blockIdx.z * px * 3 + ch, W};
+    const double *p = params + 4 * (size_t)blockIdx.z;
+    const double cx = (double)(W - 1) * 0.5, cy = (double)(H - 1) * 0.5, m = 1.0 + p[0], p1 = p[1], tx = p[2], ty = p[3];
+    const double u = (double)x - cx;
+    uint8_t *o = out + (size_t)blockIdx.z * px * 3;
+    for (int y = (int)blockIdx.y; y < H; y += (int)gridDim.y) {
+        const double v = (double)y - cy;
+        o[(size_t)y * 3 * W + e] = mag_out<uint8_t>(stab_bilinear(F, H, W, stab_sim_fx(cx, u, v, m, p1, tx), stab_sim_fy(cy, u, v, m, p1, ty)));
+    }
+}
+
 }  // namespace rm

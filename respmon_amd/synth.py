@@ -180,9 +180,8 @@ def synth_texture(H, W, seed=4321, n_waves=12, n_spots=40):
     sa = rng.uniform(-1.0, 1.0, n_spots)
     yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
 
-    def render(dx=0.0, dy=0.0):
-        x = xx - dx
-        y = yy - dy
+    def at(x, y):
+        """the texture at scene coordinates x, y [H,W] (no resampling: the analytic form is evaluated there)"""
         v = np.zeros((H, W))
         for i in range(n_waves):
             v += am[i] * np.sin(kx[i] * x + ky[i] * y + ph[i])
@@ -192,6 +191,10 @@ def synth_texture(H, W, seed=4321, n_waves=12, n_spots=40):
         g = 0.5 + 0.22 * v
         return np.clip(np.round(255 * g), 0, 255).astype(np.uint8)
 
+    def render(dx=0.0, dy=0.0):
+        return at(xx - dx, yy - dy)
+
+    render.at = at
     return render
 
 
@@ -222,6 +225,54 @@ def synth_shaky_breathing(T, H, W, jitter, seed=7, fps=10.0, breath_hz=0.4, ampl
         dx, dy = shifts[t]
         shaken[t] = np.clip(np.rint(255 * (render(dx, dy) / 255.0 + blob(dx, dy) * s[t] + n)), 0, 255).astype(np.uint8)
     return still, shaken, shifts
+
+
+def similarity_params(theta_deg, scale, tx, ty):
+    """[N,4] (p0, p1, tx, ty) of rm_stab_sim_* (include/respmon_hip.h): p0 = s cos(theta) - 1, p1 = s sin(theta)"""
+    th = np.deg2rad(np.asarray(theta_deg, dtype=np.float64))
+    s = np.asarray(scale, dtype=np.float64)
+    return np.stack(np.broadcast_arrays(s * np.cos(th) - 1.0, s * np.sin(th), np.asarray(tx, dtype=np.float64), np.asarray(ty, dtype=np.float64)), axis=-1)
+
+
+def similarity_scene_coords(H, W, p):
+    """The scene coordinates (x, y) [H,W] that a camera moved by p = (p0, p1, tx, ty) shows at its pixels: the inverse of
+    fx = cx + ((1 + p0) u - p1 v) + tx, fy = cy + (p1 u + (1 + p0) v) + ty with u = x - cx, v = y - cy, cx = (W - 1) / 2, cy = (H - 1) / 2."""
+    cx, cy = (W - 1) * 0.5, (H - 1) * 0.5
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    a, b = 1.0 + p[0], p[1]
+    X, Y = xx - cx - p[2], yy - cy - p[3]
+    n = a * a + b * b
+    return cx + (a * X + b * Y) / n, cy + (a * Y - b * X) / n
+
+
+def synth_shaky_breathing_similarity(T, H, W, jitter, rot_deg, zoom, seed=7, fps=10.0, breath_hz=0.4, amplitude=0.04, noise=0.02, center=(0.6, 0.4),
+                                     sigma=(0.10, 0.08)):
+    """synth_shaky_breathing seen by a hand-held camera: per frame the whole scene (texture and blob) is rolled about the frame's centre by
+    an angle uniform in +-`rot_deg` degrees, zoomed by a factor uniform in 1 +- `zoom` and displaced by a shift uniform in +-`jitter`
+    pixels.  The analytic texture and the blob are evaluated at the inverse-transformed coordinates, exactly: nothing is resampled.  The
+    first frame is not moved.  Returns (still, shaken, params): the uint8 [T,H,W] clip of the camera at rest, the clip of the moving
+    camera with the same breathing and the same noise, and the true parameters [T,4] (p0, p1, tx, ty) of rm_stab_sim_*."""
+    rng = np.random.Generator(np.random.PCG64([seed, 0x51a1]))
+    render = synth_texture(H, W, seed=seed)
+    params = similarity_params(rng.uniform(-rot_deg, rot_deg, T), rng.uniform(1.0 - zoom, 1.0 + zoom, T), rng.uniform(-jitter, jitter, T),
+                               rng.uniform(-jitter, jitter, T))
+    params[0] = 0.0
+    s = np.sin(2 * np.pi * breath_hz * np.arange(T) / fps)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+
+    def blob(x, y):
+        by = (y - center[0] * H) / (sigma[0] * H)
+        bx = (x - center[1] * W) / (sigma[1] * W)
+        return amplitude * np.exp(-0.5 * (by * by + bx * bx))
+
+    still, shaken = np.empty((T, H, W), np.uint8), np.empty((T, H, W), np.uint8)
+    base0, blob0 = render.at(xx, yy) / 255.0, blob(xx, yy)
+    for t in range(T):
+        n = noise * rng.standard_normal((H, W))
+        still[t] = np.clip(np.rint(255 * (base0 + blob0 * s[t] + n)), 0, 255).astype(np.uint8)
+        x, y = (xx, yy) if t == 0 else similarity_scene_coords(H, W, params[t])
+        shaken[t] = np.clip(np.rint(255 * (render.at(x, y) / 255.0 + blob(x, y) * s[t] + n)), 0, 255).astype(np.uint8)
+    return still, shaken, params
 
 
 class FakeCapture:

@@ -347,13 +347,16 @@ def phase_magnification_video(vid_data, fps, freq_min, freq_max, amplification, 
         return device.like_input(pm.push(vid), vid_data)
 
 
-def stabilize_video(vid_data, out_dtype=None, return_shifts=False, **kw):
+def stabilize_video(vid_data, out_dtype=None, return_shifts=False, model="shift", crop=False, **kw):
     """A clip of a shaky camera registered to its first frame (rm_stab_* of include/respmon_hip.h): one stabilize.Stabilizer(H, W,
     **kw), one push -- per frame the global shift against the first frame, then the bilinear warp by it.  `vid_data`: [T,H,W] gray or
     [T,H,W,3] uint8 BGR; numpy in -> numpy out, device tensor in -> device tensor out; **kw: max_shift, levels, iterations.
-    return_shifts=True: (frames, shifts [T,2], flags [T])."""
+    return_shifts=True: (frames, shifts [T,2], flags [T]).
+    model='similarity' (rm_stab_sim_*): rotation, zoom and shift, for a camera in a hand; **kw also max_linear, linear_level, and
+    return_shifts gives params [T,4] (p0, p1, tx, ty).  crop=True: the frames cut to stabilize.valid_rect(), the part the replicated
+    border cannot reach."""
     from .stabilize import stabilize_video as _stabilize_video
-    return _stabilize_video(vid_data, out_dtype=out_dtype, return_shifts=return_shifts, **kw)
+    return _stabilize_video(vid_data, out_dtype=out_dtype, return_shifts=return_shifts, model=model, crop=crop, **kw)
 
 
 def butter_lowpass_filter(data, cutoff, fs, order=5):
