@@ -411,6 +411,48 @@ int rm_rate_map(rm_ctx *ctx, const void *frames_dev, int dtype, int T, int H, in
 int rm_window_rate_map(rm_ctx *ctx, rm_window *win, double fps, double freq_min, double freq_max, int nfreq, double *freq_dev,
                        double *power_dev, double *total_dev, int32_t *index_dev, void *stream);
 
+/* ---- the pulse beside the breath: POS ("plane orthogonal to skin": Wang, den Brinker, Stuijk, de Haan, Algorithmic Principles of
+ *      Remote PPG, IEEE TBME 2017) on the three channels of an RM_BGR8 buffer.  Everything above measures luma; the pulse is a
+ *      sub-level colour change of skin, and POS projects the temporally normalised colour onto the plane orthogonal to (1, 1, 1), so
+ *      an intensity change common to the channels (a lamp, auto-exposure, a moving shadow) vanishes.  Per block of the frame it gives
+ *      a pulse map (skin is where the map is periodic), per rectangle a pulse signal for the subjects of rm_locate_multi.  Gray and
+ *      16-bit buffers carry no chroma: there is no entry point for them.
+ *      rm_bgr_block_sums: frames_dev [N,H,W,3] uint8 (channel 0, 1, 2 = B, G, R), block one of 4, 8, 16, 32, 64, Hb = ceil(H / block),
+ *        Wb = ceil(W / block); sums_dev[n][by][bx][c] (uint32) = the sum of channel c over the pixels of frame n that lie in block
+ *        (by, bx).  Edge blocks are partial and sum what is there.  The sums are exact integers (at most 64 * 64 * 255), so no order
+ *        of summation is part of the interface.  One pass over the 3 N H W bytes in one launch whatever N; any W and any byte
+ *        alignment of frames_dev are taken (16-byte loads where W % 16 == 0 and the buffer is 16-byte aligned, byte loads elsewhere).
+ *        RM_E_BADARG: NULL pointers, N, H or W < 1, a block not in the list.  RM_E_UNSUPPORTED: N * Hb >= 2^31.
+ *      rm_bgr_roi_sums: the same for K rectangles rois_host[k] = x, y, w, h (1 <= K <= RM_MAX_ROIS) of every frame, sums_dev[n][k][c],
+ *        in one launch whatever N and K.  Rectangles may overlap, repeat, be 1 x 1 or the whole frame.  rois_host is read before the
+ *        call returns.  RM_E_BADARG -- nothing is launched, nothing written -- for a rectangle that does not lie inside the frame, K
+ *        out of range, N < 1, NULL pointers.  RM_E_UNSUPPORTED: a rectangle with w * h * 255 >= 2^32, N * K >= 2^31.
+ *      rm_pulse_pos: sums_dev [N][NP][3] uint32 (NP columns: blocks or rectangles) -> h_dev [N][NP] float64, 2 <= window = l <= N <=
+ *        4096.  Everything is float64, every operation rounds once (no contraction).  For column p and every window start
+ *        n = 0 .. N - l:
+ *          S_c   = sum_{k<l} s[n+k][p][c]                  integer, exact (uint64); any S_c == 0: the window contributes nothing
+ *          x_c,k = ((double)s[n+k][p][c] * (double)l) / (double)S_c      (the product is exact: x is the correctly rounded ratio)
+ *          S1_k  = x_G,k - x_B,k           S2_k = (x_G,k + x_B,k) - 2.0 * x_R,k
+ *          v1    = sum_k S1_k * S1_k       v2   = sum_k S2_k * S2_k       ascending k, from 0.0
+ *          a     = v2 > 0 ? sqrt(v1 / v2) : 0
+ *          h_n,k = S1_k + a * S2_k
+ *          H[t][p] = sum_n h_n,(t-n)  over n = max(0, t - l + 1) .. min(t, N - l), ascending n, from 0.0
+ *        This is the published algorithm; the time mean of each normalised channel over its window is exactly 1, so the means of S1,
+ *        S2 and h are 0 in exact arithmetic and the published mean subtractions are left out (the textbook form agrees to ~1e-14
+ *        relative).  The per-window S_c and a live in the context's workspace: RM_E_BUSY as rm_rate_map.  RM_E_BADARG: NULL pointers,
+ *        N < 2, window outside 2..N.  RM_E_UNSUPPORTED: N > 4096.  NP == 0 is an empty call.
+ *      rm_pulse_map: rm_bgr_block_sums, then rm_pulse_pos on [N][Hb * Wb][3], then the estimator of rm_spectral_peak on H[N][Hb * Wb];
+ *        outputs [Hb * Wb] each, any may be NULL (not all).  Bit for bit what the three calls give one after the other.  The
+ *        intermediates live in the context's workspace: RM_E_BUSY as rm_rate_map.  Band, nfreq and N refusals are rm_spectral_peak's
+ *        (T = N); RM_E_BADARG also for a block not in the list and a window outside 2..N.  Nothing is written on a refusal.
+ *      All four are asynchronous on `stream`. */
+int rm_bgr_block_sums(rm_ctx *ctx, const uint8_t *frames_dev, int N, int H, int W, int block, uint32_t *sums_dev, void *stream);
+int rm_bgr_roi_sums(rm_ctx *ctx, const uint8_t *frames_dev, int N, int H, int W, const int32_t *rois_host, int K, uint32_t *sums_dev,
+                    void *stream);
+int rm_pulse_pos(rm_ctx *ctx, const uint32_t *sums_dev, int N, size_t NP, int window, double *h_dev, void *stream);
+int rm_pulse_map(rm_ctx *ctx, const uint8_t *frames_dev, int N, int H, int W, int block, int window, double fps, double freq_min,
+                 double freq_max, int nfreq, double *freq_dev, double *power_dev, double *total_dev, int32_t *index_dev, void *stream);
+
 /* ---- a LIVE stream magnified chunk by chunk: the causal band-pass of rm_sosfilt with carried state.  rm_magnify's band-pass is
  *      the reference's FFT operator, which is even in time: its newest frame mixes in motion of the oldest frame of the buffer.  An
  *      rm_stream holds the filter state of every filtered pyramid element instead of a [T,H,W] buffer: each pushed chunk comes back

@@ -104,6 +104,10 @@ SIGNATURES = {
     "rm_spectral_peak": (_i, [_vp, _vp, _i, _sz, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "rm_rate_map": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "rm_window_rate_map": (_i, [_vp, _vp, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "rm_bgr_block_sums": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "rm_bgr_roi_sums": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "rm_pulse_pos": (_i, [_vp, _vp, _i, _sz, _i, _vp, _vp]),
+    "rm_pulse_map": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "rm_stream_create": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _d, _c.POINTER(_vp)]),
     "rm_stream_destroy": (_i, [_vp]),
     "rm_stream_reset": (_i, [_vp, _vp]),

@@ -870,6 +870,24 @@ class RespiratoryMonitor(BreathSignal):
             freq_max = self.freq_max if self is not None else 1.0
         return rate.buffer_rate_map(frames, fps, freq_min, freq_max, 4 if level is None else level, nfreq)
 
+    @rate.static_or_instance
+    def pulse_map(self, frames=None, fps=None, block=16, window=None, freq_min=0.7, freq_max=3.0, nfreq=64):
+        """Where the pulse shows and how fast it is: a rate.RateMap over blocks of `block` x `block` pixels (level = log2(block)) from
+        the POS projection of the three colour channels (pulse.pulse_map, rm_pulse_map) -- skin is where `periodicity` is high, and
+        roi_bpm takes the rectangles of locate_all().  On a monitor the defaults are its calibration buffer and fps;
+        RespiratoryMonitor.pulse_map(frames, fps) is the static form.  The band is the pulse's (0.7 - 3.0 Hz), not the monitor's
+        breathing band.  Needs buffer_dtype 'bgr8': a gray buffer holds no pulse signal for POS (ValueError)."""
+        from . import pulse
+        if frames is None:
+            if self is None:
+                raise TypeError("RespiratoryMonitor.pulse_map(frames, fps): the static form needs the frames")
+            frames = self.calibration_buffer
+        if fps is None:
+            if self is None:
+                raise TypeError("RespiratoryMonitor.pulse_map(frames, fps): the static form needs fps")
+            fps = self.fps
+        return pulse.pulse_map(frames, fps, block, window, freq_min, freq_max, nfreq)
+
     calibrate = locate  # north_star names a calibrate(); the reference's calibration entry is locate()
 
     def magnified_calibration_video(self, out_dtype=None, color=False, method='linear', amplification=None):

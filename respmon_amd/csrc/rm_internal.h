@@ -21,6 +21,7 @@
 //   rm_phase_motion.hip   rm_phase_motion_*: the 'phase' motion signal of extract_motion, K subjects and a clip per call (rm_phase_motion_kernels.h)
 //   rm_stabilize.hip      rm_stab_*, rm_warp_shift: the global shift of a frame against a reference frame and the warp that takes it out;
 //                         rm_stab_sim_*, rm_warp_similarity: the same for rotation, zoom and shift (rm_stabilize_kernels.h)
+//   rm_pulse.hip          rm_bgr_block_sums, rm_bgr_roi_sums, rm_pulse_pos, rm_pulse_map: per-channel sums of a BGR buffer, the POS pulse signal, the pulse map (rm_pulse_kernels.h)
 //   rm_unity.hip          all of the above as ONE unit: the tracing build and the host emulation of the tests
 // A kernel is compiled in the ONE unit that launches it.  This header therefore includes no kernel header beyond what its own
 // declarations need (rm_kernels.h: the geometry structs, CollapseState, SumPlan; rm_flow_ws.h: rm_ctx embeds a FlowWorkspace) and what

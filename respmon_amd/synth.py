@@ -166,6 +166,26 @@ def synth_brightness_video(T, H, W, fps=10.0, hz=0.4):
     return np.broadcast_to(lvl[:, None, None, None], (T, H, W, 3)).copy()
 
 
+def synth_pulse_bgr(N, H, W, fps=20.0, seed=0, pulse_hz=1.25, flicker_hz=0.9, skin=(110.0, 140.0, 200.0), background=(120.0, 120.0, 120.0),
+                    pulse=(0.53, 0.77, 0.33), pulse_depth=0.004, flicker_depth=0.02, noise=1.0):
+    """A pulse under a flickering lamp, BGR uint8 [N,H,W,3]: the left half of the frame is skin of colour `skin` (B, G, R) whose channels
+    carry the relative pulsatile term pulse_depth * pulse * sin(2 pi pulse_hz t), the right half a gray wall; every pixel is multiplied
+    by the lamp's 1 + flicker_depth * sin(2 pi flicker_hz t), Gaussian noise of `noise` levels is added and the result rounded.  The
+    flicker is five times the pulse in every channel: a gray or single-channel mean sees the lamp, POS sees the pulse."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(N) / float(fps)
+    base = np.empty((H, W, 3))
+    base[:, :W // 2] = skin
+    base[:, W // 2:] = background
+    mod = np.ones((N, 1, W, 3))
+    mod[:, :, :W // 2, :] += pulse_depth * np.asarray(pulse, dtype=np.float64)[None, None, None, :] * np.sin(2 * np.pi * pulse_hz * t)[:, None, None, None]
+    lamp = 1.0 + flicker_depth * np.sin(2 * np.pi * flicker_hz * t)
+    out = np.empty((N, H, W, 3), np.uint8)
+    for n in range(N):
+        out[n] = np.clip(np.rint(base * mod[n] * lamp[n] + noise * rng.standard_normal((H, W, 3))), 0, 255).astype(np.uint8)
+    return out
+
+
 def synth_texture(H, W, seed=4321, n_waves=12, n_spots=40):
     """Config 3: analytic texture (random 2-D sinusoids + Gaussian spots) as a callable
     f(dx, dy) -> uint8 [H,W] rendered at a sub-pixel shift, so ground-truth flow is known."""
