@@ -70,7 +70,9 @@ extern "C" {
 #define RM_FLAG_UNFUSED_SMALL 16u /* build / collapse the small pyramid with one launch per level (A/B + fallback path) */
 #define RM_FLAG_CONTOUR_CLIP_FRAME 32u /* rm_locate: cv2.findContours as OpenCV <= 3.1 did it (see rm_set_contour_clip_frame) */
 #define RM_FLAG_FILTER_LAPLACIANS 64u /* build the small pyramid in the reference's order -- Laplacians first, filter them, collapse (bit for bit equal to the per-level
-                                         path) -- instead of the filter-first form (filter G_S, then Laplacians + collapse in one kernel; equal to ~1e-15) */
+                                         path) -- instead of the filter-first form (filter G_S, then Laplacians + collapse in one kernel; equal to ~1e-15).
+                                         Frames whose level skip_levels_at_top is a single pixel: the Laplacians (zero but for rounding there) are
+                                         taken from G_S before the filter in either form; what a window or rm_shard_pyramid stores does not change. */
 #define RM_FLAG_DENSE_SUM 128u    /* take the masked time sum with the dense kernel (recomputes every value, no value store) ... */
 #define RM_FLAG_SPARSE_SUM 256u   /* ... or with the sparse path (evaluate + store the pairs that can fall below `top`).  Neither: decided on
                                      the device from what THIS call's selection kept (nothing is remembered between calls): dense when the

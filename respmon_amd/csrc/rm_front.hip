@@ -195,6 +195,20 @@ int front_filter(rm_ctx *ctx, const double *lap, int T, const PyrGeom &pg, doubl
     const int L = pg.L, S = pg.S;
     const size_t NP = pg.NP;
     const int Th = sym_frames(T);   // the band-passed signal is even in time: everything below handles the unique frames only
+    if (pg.filter_first && (size_t)h[S] * w[S] == 1) {
+        // A level S of one pixel: every filtered level is one pixel and its Laplacian x - pyrUp(pyrDown(x)) is zero but for the rounding
+        // of the two steps.  Filtering G_S first would amplify x before that cancellation and leave ulp(amplification * x) where the
+        // reference has amplification * ulp(x) or an exact zero.  The rows stay G_S (a window's ring, rm_shard_pyramid's output and
+        // rm_window_rate_map see no difference); the Laplacians are taken from them here, before the filter, in the reference's order.
+        PyrGeom lf;
+        pyr_geom(h[0], w[0], L, S, RM_FLAG_FILTER_LAPLACIANS, lf);
+        double *lap1 = nullptr;
+        RM_TRY(ws(ctx, "lap_one_pixel", (size_t)T * lf.NP, &lap1));
+        hipLaunchKernelGGL(k_small_pyramid<>, dim3(T), dim3(SMALL_NT), lf.lds_levels * sizeof(double), s, lap, lf.sg, lap1, ctx->d_state);
+        LAUNCH_CHECK();
+        ctx->state_fresh = true;
+        return front_filter(ctx, lap1, T, lf, fps, fmin, fmax, amp, out, s, head);
+    }
     out.h = pg.h; out.w = pg.w; out.S = S; out.all_zero = false;
     // consumed here, on every path: whatever follows reduces into d_state, so the reset by front_pyramid's last kernel
     // vouches for this call only (a later rm_shard_collapse with a foreign lap buffer must reset the state itself)

@@ -22,6 +22,7 @@ from respmon_amd import _capi, synth
 from tests import stabilize_reference as sr
 
 RECORDED_D = 8.4e-15       # px; 64 D = 5.4e-13 px, so the floor of 2^-40 = 9.1e-13 px is the bound (the emulated build lands at 3.4e-15 px)
+                           # (on the 66- to 195-tile frames of tests/geometry_cases.py, by the same rule: 2.2e-14 px)
 FACTOR, FLOOR = 64, 2.0 ** -40
 SENTINEL = 7
 
@@ -72,6 +73,7 @@ def clip(H, W, max_shift, kind="u8"):
 
 
 # name -> (H, W, level_coarse, level_fine, max_shift, kind).  The reduction tile is 64 x 16, pyrDown's 64 x 8, a warp workgroup 256 elements.
+# No case here has more than 12 tiles: the folds over more than 64 tiles and the warps' row cap are in tests/geometry_cases.py.
 ESTIMATE_CASES = {
     "48x64": (48, 64, 2, 0, 4.0, "u8"), "45x67_odd": (45, 67, 2, 0, 4.0, "u8"),
     "96x128_l31": (96, 128, 3, 1, 8.0, "u8"), "96x128_l20": (96, 128, 2, 0, 8.0, "u8"),

@@ -19,6 +19,7 @@ from tests import stabilize_reference as sr
 from tests import stabilize_sim_reference as ssr
 
 RECORDED_D = 2.9e-14       # px; 64 D = 1.8e-12 px, above the floor of 2^-40 = 9.1e-13 px
+                           # (on the 66- to 195-tile frames of tests/geometry_cases.py, by the same rule: 2.3e-13 px)
 FACTOR, FLOOR = 64, 2.0 ** -40
 SENTINEL = sc.SENTINEL
 N = 9
