@@ -401,7 +401,49 @@ template <typename F> void run_grid(dim3 grid, dim3 block, F &&body) {
 }
 }  // namespace hipemu
 
+// The launch census (test infrastructure; DESIGN.md "Launch census").  Every hipLaunchKernelGGL the compiler
+// instantiates names one kernel instance; site<K> puts that instance on a process-wide list when the library is
+// loaded (the universe), and the macro marks it when control passes through (the launched set).  Tests read both
+// through the three rm_emu_census_* functions below, which only this emulated library exports.
+namespace hipemu {
+struct CensusEntry { const char *pretty; std::atomic<unsigned char> launched; CensusEntry *next; };
+inline CensusEntry *&census_head() { static CensusEntry *h = nullptr; return h; }
+template <auto K> struct site {
+    // g++: "... [with auto K = rm::k_rate_peak<3, 0>]" -- the resolved template arguments come with the name
+    static const char *pretty() { return __PRETTY_FUNCTION__; }
+    struct Reg {
+        CensusEntry e;
+        Reg() { e.pretty = pretty(); e.launched = 0; e.next = census_head(); census_head() = &e; }
+    };
+    inline static Reg reg;
+    static void mark() { reg.e.launched.store(1, std::memory_order_relaxed); }
+};
+// newline-separated instance names into buf (at most cap bytes, NUL-terminated); returns the bytes the whole list needs
+inline size_t census_list(bool launched_only, char *buf, size_t cap) {
+    size_t need = 1, at = 0;
+    for (CensusEntry *e = census_head(); e; e = e->next) {
+        if (launched_only && !e->launched.load(std::memory_order_relaxed)) continue;
+        const char *b = std::strstr(e->pretty, "K = ");
+        b = b ? b + 4 : e->pretty;
+        const char *z = std::strrchr(b, ']');
+        size_t n = z ? (size_t)(z - b) : std::strlen(b);
+        need += n + 1;
+        if (buf && at + n + 2 <= cap) { std::memcpy(buf + at, b, n); at += n; buf[at++] = '\n'; }
+    }
+    if (buf && cap) buf[at < cap ? at : cap - 1] = 0;
+    return need;
+}
+}  // namespace hipemu
+
+extern "C" {
+__attribute__((used, visibility("default"))) inline size_t rm_emu_census_universe(char *buf, size_t cap) { return hipemu::census_list(false, buf, cap); }
+__attribute__((used, visibility("default"))) inline size_t rm_emu_census_launched(char *buf, size_t cap) { return hipemu::census_list(true, buf, cap); }
+__attribute__((used, visibility("default"))) inline void rm_emu_census_reset() {
+    for (hipemu::CensusEntry *e = hipemu::census_head(); e; e = e->next) e->launched.store(0, std::memory_order_relaxed);
+}
+}
+
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    hipemu::run_grid(dim3(grid), dim3(block), [&] { kernel(__VA_ARGS__); })
+    (hipemu::site<kernel>::mark(), hipemu::run_grid(dim3(grid), dim3(block), [&] { kernel(__VA_ARGS__); }))
 
 #endif

@@ -27,6 +27,31 @@ def buf_args(frames):
     return T, H, W, DT[frames.dtype]
 
 
+def _census_list(lib, fn):
+    f = getattr(lib, fn)
+    f.restype = ctypes.c_size_t
+    f.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+    need = f(None, 0)
+    buf = ctypes.create_string_buffer(need)
+    f(buf, need)
+    return frozenset(s for s in buf.value.decode().split("\n") if s)
+
+
+def census_universe(lib):
+    """Every kernel instantiation the emulated library can launch (the launch census of tests/emu's hip_runtime.h)."""
+    return _census_list(lib, "rm_emu_census_universe")
+
+
+def census_launched(lib):
+    """The instantiations launched since the library was loaded or census_reset()."""
+    return _census_list(lib, "rm_emu_census_launched")
+
+
+def census_reset(lib):
+    lib.rm_emu_census_reset.restype = None
+    lib.rm_emu_census_reset()
+
+
 class Emu:
     def __init__(self):
         from tests.emu import build as emu_build

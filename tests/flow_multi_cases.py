@@ -86,20 +86,22 @@ class EmuApi:
                                                float(begin[2]), int(begin[3]), ptr(pts), ctypes.byref(n), None), "flow_begin")
         return None if n.value == 0 else pts[:n.value].reshape(-1, 1, 2).copy()
 
-    def step(self, st, frame, roi):
+    def step(self, st, frame, roi, win=None):
         f = np.ascontiguousarray(frame)
+        win = win or WIN
         from tests.emu_harness import DT, ptr
         m = np.empty(2, np.float32); ng = ctypes.c_int()
-        self.emu.ck(self.emu.lib.rm_flow_step(self.emu.ctx, st, ptr(f), DT[f.dtype], f.shape[0], f.shape[1], *roi, WIN[0], WIN[1], LVL, CRIT[1],
+        self.emu.ck(self.emu.lib.rm_flow_step(self.emu.ctx, st, ptr(f), DT[f.dtype], f.shape[0], f.shape[1], *roi, win[0], win[1], LVL, CRIT[1],
                                               float(CRIT[2]), ptr(m), ctypes.byref(ng), None), "flow_step")
         return m, ng.value
 
-    def clip(self, st, frames, roi):
+    def clip(self, st, frames, roi, win=None):
         f = np.ascontiguousarray(frames)
+        win = win or WIN
         from tests.emu_harness import DT, ptr
         N, H, W = f.shape
         m = np.empty((N, 2), np.float32); ng = np.empty(N, np.int32)
-        self.emu.ck(self.emu.lib.rm_flow_clip(self.emu.ctx, st, ptr(f), DT[f.dtype], N, H, W, *roi, WIN[0], WIN[1], LVL, CRIT[1], float(CRIT[2]),
+        self.emu.ck(self.emu.lib.rm_flow_clip(self.emu.ctx, st, ptr(f), DT[f.dtype], N, H, W, *roi, win[0], win[1], LVL, CRIT[1], float(CRIT[2]),
                                               ptr(m), ptr(ng), None), "flow_clip")
         return m, ng
 
@@ -119,8 +121,8 @@ class EmuApi:
                                              lvl, CRIT[1], float(CRIT[2]), None if "mean" in null else ptr(m), None if "n_good" in null else ptr(ng), None)
         return rc, m, ng
 
-    def multi(self, states, frames, rois):
-        rc, m, ng = self.multi_rc(states, frames, rois)
+    def multi(self, states, frames, rois, win=None):
+        rc, m, ng = self.multi_rc(states, frames, rois, win=win or WIN)
         self.emu.ck(rc, "flow_multi_clip")
         return m, ng
 
@@ -175,14 +177,14 @@ class GpuApi:
     def begin(self, st, frame, roi, begin=BEGIN):
         return self.be.flow_begin(st, frame, *roi, *begin)
 
-    def step(self, st, frame, roi):
-        return self.be.flow_step(st, frame, *roi, **LK)
+    def step(self, st, frame, roi, win=None):
+        return self.be.flow_step(st, frame, *roi, **dict(LK, winSize=win or WIN))
 
-    def clip(self, st, frames, roi):
-        return self.be.flow_clip(st, frames, *roi, **LK)
+    def clip(self, st, frames, roi, win=None):
+        return self.be.flow_clip(st, frames, *roi, **dict(LK, winSize=win or WIN))
 
-    def multi(self, states, frames, rois):
-        return self.be.flow_multi_clip(states, frames, rois, **LK)
+    def multi(self, states, frames, rois, win=None):
+        return self.be.flow_multi_clip(states, frames, rois, **dict(LK, winSize=win or WIN))
 
     def points(self, st, cap=100):
         return self.be.flow_points(st, cap)
@@ -216,10 +218,10 @@ def begin_all(api, frame0, rois, begins=None):
     return states, pts
 
 
-def run(api, frames, rois, schedule, begins=None, caps=None):
+def run(api, frames, rois, schedule, begins=None, caps=None, win=None):
     """States begun on frames[0], then the schedule over the following frames.  An entry is (form, n): 'multi' = one
     rm_flow_multi_clip of n frames for all subjects, 'clip' = one rm_flow_clip of n frames per subject, 'step' = n rm_flow_step per
-    subject.  No subject ever skips a frame: only the call form changes.
+    subject.  No subject ever skips a frame: only the call form changes.  win: the LK window of every call (None: WIN).
     -> dict(states, pts0, mean [T,K,2], n_good [T,K], points [K] as rm_flow_points returns them afterwards)"""
     K = len(rois)
     states, pts0 = begin_all(api, frames[0], rois, begins)
@@ -227,17 +229,17 @@ def run(api, frames, rois, schedule, begins=None, caps=None):
     for form, n in schedule:
         f = frames[t:t + n]
         if form == "multi":
-            m, ng = api.multi(states, f, rois)
+            m, ng = api.multi(states, f, rois, win)
             m, ng = np.array(m, np.float32), np.array(ng, np.int32)
         else:
             m, ng = np.zeros((n, K, 2), np.float32), np.zeros((n, K), np.int32)
             for k in range(K):
                 if form == "clip":
-                    mk, nk = api.clip(states[k], f, rois[k])
+                    mk, nk = api.clip(states[k], f, rois[k], win)
                     m[:, k], ng[:, k] = mk, nk
                 else:
                     for i in range(n):
-                        mk, nk = api.step(states[k], f[i], rois[k])
+                        mk, nk = api.step(states[k], f[i], rois[k], win)
                         m[i, k], ng[i, k] = mk, nk
         means.append(m); ngs.append(ng)
         t += n
@@ -350,3 +352,46 @@ def step_in_clips(obj, frames, sizes):
             break
         obj.step_clip(frames[t:t + n])
         t += n
+
+
+# ---- the instances of the clip driver that the cases above do not select -----------------------------------------------------------
+def check_schedule_and_oracle(api, frames, rois, begins, caps, win, n):
+    """n frames after frames[0] with the LK window `win`: one rm_flow_multi_clip and the per-subject clips against the rm_flow_step loop,
+    bit for bit, and that loop against the oracle's calcOpticalFlowPyrLK on the crops the reference forms (base.py:364-388): the same
+    survivors, and the mean of old - new over them, bit for bit.  -> the loop's run"""
+    from tests import geometry_cases as gc
+    oracle = gc.oracle()
+    dev = api.dev(frames)
+    steps = run(api, dev, rois, [("step", n)], begins, caps, win)
+    assert_same(run(api, dev, rois, [("multi", n)], begins, caps, win), steps, ("multi", win))
+    assert_same(run(api, dev, rois, [("clip", n)], begins, caps, win), steps, ("clip", win))
+    for k, (x, y, w, h) in enumerate(rois):
+        crops = [np.ascontiguousarray(oracle.float_to_uint8(oracle.uint8_to_float(f)[y:y + h, x:x + w])) for f in frames[:n + 1]]
+        cur = steps["pts0"][k]
+        assert cur is not None and len(cur) > 0, k
+        for t in range(1, n + 1):
+            r1, rs, _ = oracle.calcOpticalFlowPyrLK(crops[t - 1], crops[t], cur, None, winSize=tuple(win), maxLevel=LVL, criteria=CRIT)
+            good = rs.ravel() == 1
+            assert steps["n_good"][t - 1, k] == int(good.sum()) and good.any(), (k, t)
+            assert np.array_equal(steps["mean"][t - 1, k], np.mean(cur.reshape(-1, 2)[good] - r1.reshape(-1, 2)[good], axis=0)), (k, t)   # base.py:388
+            cur = r1[good].reshape(-1, 1, 2)
+        assert np.array_equal(np.asarray(steps["points"][k]).reshape(-1, 2), cur.reshape(-1, 2)), k
+    return steps
+
+
+WIDE_WINDOWS = ((17, 17), (21, 21))          # win_w * win_h > 256: the sixteen-pixels-per-lane instance of the clip tracker
+
+
+def check_wide_window(api, win):
+    check_schedule_and_oracle(api, frames_emu(1.0, 5), ROIS_EMU[:3], None, None, win, 4)
+
+
+MANY = dict(H=440, W=460, begin=(7000, 0.0001, 1, 3), win=(3, 3))      # more points than the LDS staging of the finish holds (FLOW_FINISH_MAX = 6000)
+
+
+def check_many_points(api):
+    """a subject of 7000 points (the sequential finish of rm_flow_step and of rm_flow_multi_clip) beside one of a few"""
+    render = synth.synth_texture(MANY["H"], MANY["W"], seed=5)
+    frames = np.stack([render(0.7 * np.sin(0.5 * t), 0.3 * np.cos(0.4 * t)) for t in range(3)])
+    steps = check_schedule_and_oracle(api, frames, [(0, 0, MANY["W"], MANY["H"]), (10, 10, 24, 20)], [MANY["begin"], BEGIN], [MANY["begin"][0], 100], MANY["win"], 2)
+    assert len(steps["pts0"][0]) == MANY["begin"][0] and steps["n_good"][-1, 0] > 6000      # still above the staging after the last step

@@ -96,7 +96,7 @@ def same_bits(a, b):
 # the shapes of the issue, and two rows wider than one wave of 16-pixel groups (65 groups: a second workgroup column), one that takes
 # the 16-byte loads (1040 = 16 * 65) and one that does not
 SHAPES = ((1, 1), (3, 5), (16, 16), (17, 37), (33, 64), (40, 129), (5, 1040), (3, 1030))
-BLOCKS = (4, 16, 64)
+BLOCKS = (4, 8, 16, 32, 64)       # every size pulse_block_ok takes: NB = 4, 2 and the fold over L = 1, 2, 4 lanes
 
 
 @functools.lru_cache(maxsize=None)
@@ -227,7 +227,7 @@ def check_pos(be, N, l):
 
 # ---- case 4: rm_pulse_map equals its three parts ------------------------------------------------------------------------------------
 MAP_BAND = dict(fps=20.0, fmin=0.7, fmax=3.0, F=17)
-MAP_GEOMS = ((17, 37, 4), (40, 129, 16))
+MAP_GEOMS = ((17, 37, 4), (40, 129, 16), (33, 64, 8), (40, 129, 32))
 
 
 @functools.lru_cache(maxsize=None)

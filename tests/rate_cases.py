@@ -319,6 +319,67 @@ def check_peak(be, T, F):
     return figs
 
 
+# ---- case 1 at NH = 3 (33 <= nfreq <= 48), the instance FS never selected ------------------------------------------------------------
+NH3_FS = (33, 48)                       # the two ends of NH = 3
+NH3_TS = (3, 16, 33, 128)
+NH3_NPS = (1, 15, 16, 17, 63, 65)
+# frames whose level 1 has exactly NP pixels, for the ring arm (rm_window_rate_map reads the window's own level-S rows)
+NH3_RING_GEOMS = {1: (2, 2), 15: (6, 10), 16: (8, 8), 17: (2, 34), 63: (14, 18), 65: (10, 26)}
+
+
+def reference_caps(ref, n, tag):
+    """what check_against demands of the REFERENCE on its first n columns (no library): at most 1 % ambiguous pixels, at most 1 % whose
+    frequency bound exceeds 1e-6"""
+    r = RefCols(ref, n)
+    mv = ~r.still
+    n_amb = int(r.ambiguous.sum())
+    assert n_amb <= 0.01 * n, (tag, "ambiguous pixels", n_amb, n)
+    fin = mv & ~r.ambiguous & r.inner
+    n_loose = int((fin & ~(r.delta_bound < 1e-6)).sum())
+    assert n_loose <= 0.01 * n, (tag, "pixels whose frequency bound exceeds 1e-6", n_loose, n)
+
+
+@functools.lru_cache(maxsize=None)
+def ring_frames(N, H, W):
+    """uint8 [N, H, W]: every pixel swings by 60 levels at a rate of its own inside RM_KW's band, plus two levels of noise"""
+    rng = np.random.default_rng(100 * H + W)
+    f0 = RM_KW["fmin"] + (RM_KW["fmax"] - RM_KW["fmin"]) * rng.random((1, H, W))
+    t = np.arange(N)[:, None, None]
+    v = 128 + 60 * np.sin(2 * np.pi * f0 * t / RM_KW["fps"] + 2 * np.pi * rng.random((1, H, W))) + rng.integers(-2, 3, (N, H, W))
+    v = np.rint(v).astype(np.uint8)
+    v.setflags(write=False)
+    return v
+
+
+def check_peak_form(be, T, F, wide, nps=NH3_NPS):
+    """every NP of nps in ONE form against the reference (check_peak's inputs and reference)"""
+    x, ref = _ref_case1(T, F)
+    for n in nps:
+        with Form(be, wide):
+            got = peak(be, x[:, :n], BAND["fps"], BAND["fmin"], BAND["fmax"], F)
+        check_against(RefCols(ref, n), *got, tag=(T, F, n, wide))
+
+
+def check_ring_form(be, T, F, wide, nps=NH3_NPS):
+    """the ring arm in one form: a window of T frames whose head has wrapped, rm_window_rate_map against rm_spectral_peak on the unrolled
+    window (rm_pyr_down of the frames it holds) bit for bit, as check_window does"""
+    kw = RM_KW
+    for n in nps:
+        H, W = NH3_RING_GEOMS[n]
+        assert int(np.prod(level_shape(H, W, 1))) == n
+        v = ring_frames(T + 2, H, W)
+        k = T + 2                                     # two frames past a full window: the head is inside the ring
+        with wc.Window(be, T, H, W, 3, 1) as win:
+            win.push_np(v[:T])
+            win.push_np(v[T:k])
+            outs = Outs(be, n)
+            with Form(be, wide):
+                _capi.check(be.lib, window_rate_map_rc(be, win, kw["fps"], kw["fmin"], kw["fmax"], F, outs), "rm_window_rate_map")
+                want = peak(be, pyr_down_n(be, v[k - T:k], 1), kw["fps"], kw["fmin"], kw["fmax"], F)
+        same_outputs(outs.np(), want, ("ring", T, F, n, wide))
+        assert (want[3] >= 0).all(), ("ring", T, F, n, wide)          # every pixel moves: the comparison is not one of empty maps
+
+
 def sample_columns(n, k=96):
     """columns of a wide case that meet the reference: both ends and a spread"""
     rng = np.random.default_rng(n)

@@ -489,3 +489,71 @@ def check_table(H=65, W=129):
     assert [c.name for c in small if c.name.startswith("f_")] == ["f_frame_only_3x3"]
     fo = next(c for c in small if c.name.startswith("f_"))
     assert fo.winner(False) == (0, 0, 3, 3) and fo.winner(True) is None
+
+
+# ---- check_product's backend interface on the two builds (tests/test_emu_roi_reference.py, tests/test_gpu_roi_reference.py,
+# tests/instantiation_cases.py) -------------------------------------------------------------------------------------------------
+class EmuRoi:
+    """on the emulated C-ABI (tests/emu_harness.py Emu)"""
+
+    def __init__(self, emu):
+        self.emu = emu
+        self.paths = set()
+
+    def dev(self, heat):
+        return heat
+
+    def roi(self, heat, clip, labelling):
+        roi = self.emu.heatmap_to_roi(heat, THRESHOLD, clip_frame=clip, labelling=1 if labelling else 0)[0]
+        self.paths.add(self.emu.roi_path())
+        return roi
+
+    def rois(self, heat, H, W, K, min_area, clip):
+        from tests import subjects_cases as sc
+        from tests.emu_harness import ptr
+        return sc.heatmap_to_rois(self.emu.lib, self.emu.ctx, ptr(heat), H, W, K, min_area, threshold=THRESHOLD, clip=clip)
+
+    def set(self, key, value):
+        self.emu.debug_set(key, value)
+
+    def stats(self):
+        return self.emu.contour_stats()
+
+    def path(self):
+        return self.emu.roi_path()
+
+
+class GpuRoi:
+    """on the product's C-ABI (device heat maps)"""
+
+    def __init__(self):
+        import torch
+        assert torch.cuda.is_available()
+        from respmon_amd import _capi, device, dist
+        self.torch, self.device, self.dist = torch, device, dist
+        self.lib, self.ctx = _capi.load(), device.ctx()
+        self.paths = set()
+
+    def dev(self, heat):
+        return self.torch.from_numpy(np.ascontiguousarray(heat)).cuda()
+
+    def roi(self, heat, clip, labelling):
+        roi = self.dist.hip_heatmap_to_roi(heat, THRESHOLD, clip_frame=clip, labelling=bool(labelling))
+        self.paths.add(self.dist.roi_path())
+        return roi
+
+    def rois(self, heat, H, W, K, min_area, clip):
+        import ctypes
+        from tests import subjects_cases as sc
+        return sc.heatmap_to_rois(self.lib, self.ctx, ctypes.c_void_p(heat.data_ptr()), H, W, K, min_area, threshold=THRESHOLD, clip=clip,
+                                  stream=self.device.stream_ptr())
+
+    def set(self, key, value):
+        self.device.debug_set(key, value)
+
+    def stats(self):
+        n, labelled = self.dist.contour_stats()
+        return n, int(labelled)
+
+    def path(self):
+        return self.dist.roi_path()

@@ -18,8 +18,9 @@ import numpy as np
 from respmon_amd import _capi, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DT = {np.dtype(np.uint8): _capi.RM_U8, np.dtype(np.float16): _capi.RM_F16, np.dtype(np.float32): _capi.RM_F32, np.dtype(np.float64): _capi.RM_F64}
-OUT_NP = {_capi.RM_U8: np.uint8, _capi.RM_F32: np.float32, _capi.RM_F64: np.float64}
+DT = {np.dtype(np.uint8): _capi.RM_U8, np.dtype(np.uint16): _capi.RM_U16, np.dtype(np.float16): _capi.RM_F16, np.dtype(np.float32): _capi.RM_F32,
+      np.dtype(np.float64): _capi.RM_F64}
+OUT_NP = {_capi.RM_U8: np.uint8, _capi.RM_U16: np.uint16, _capi.RM_F32: np.float32, _capi.RM_F64: np.float64}
 
 # ---- the filter ---------------------------------------------------------------------------------------------------------------
 SOS_ORDERS = (1, 2, 6, 8)
@@ -100,6 +101,41 @@ def check_sosfilt(be, order, rate):
                 got = sosfilt(be, sos, x, zi=zi, scale=scale)
                 want, _ = sos_restated(sos, x, z=z0, scale=scale)
                 assert np.array_equal(got, want), (order, rate, T, NP, scale, "zi", np.abs(got - want).max())
+                assert np.abs(got - scipy.signal.sosfilt(sos, x, axis=0, zi=z0)[0] * scale).max() <= 1e-12
+
+
+# the section counts no integer-order design of SOS_ORDERS gives: a low-pass design followed by a band-pass one, so that every section
+# has coefficients of its own and the low-pass sections (DC gain != 0) have a steady state that is not zero
+SOS_MIXED = {3: (2, 2), 4: (4, 2), 5: (4, 3), 7: (6, 4)}        # sections -> (low-pass order: order / 2 sections, band-pass order)
+
+
+def mixed_sos(nsec, fps, fmin, fmax):
+    import scipy.signal
+    lo, bp = SOS_MIXED[nsec]
+    sos = np.concatenate([scipy.signal.butter(lo, 2.5 * fmax / (fps / 2), btype='low', output='sos'), butter_sos(bp, fps, fmin, fmax)])
+    assert sos.shape == (nsec, 6) and np.all(sos[:, 3] == 1.0) and len({tuple(r) for r in sos}) == nsec
+    return np.ascontiguousarray(sos)
+
+
+def check_sosfilt_sections(be, nsec, rate, Ts=SOS_T, NPs=SOS_NP):
+    """check_sosfilt for a table of `nsec` sections that is not one design: from rest and from zi, bit for bit"""
+    import scipy.signal
+    sos = mixed_sos(nsec, *rate)
+    zi = sosfilt_zi(sos)
+    assert np.abs(zi[:SOS_MIXED[nsec][0] // 2 + 1]).min() > 0        # the steady state reaches past the low-pass sections
+    rng = np.random.default_rng(100 * nsec + int(rate[0]))
+    for T in Ts:
+        for NP in NPs:
+            x = rng.random((T, NP))
+            for scale in SOS_SCALES:
+                got = sosfilt(be, sos, x, scale=scale)
+                want, _ = sos_restated(sos, x, scale=scale)
+                assert np.array_equal(got, want), (nsec, rate, T, NP, scale, np.abs(got - want).max())
+                assert np.abs(got - scipy.signal.sosfilt(sos, x, axis=0) * scale).max() <= 1e-12
+                z0 = steady_state(zi, x[0])
+                got = sosfilt(be, sos, x, zi=zi, scale=scale)
+                want, _ = sos_restated(sos, x, z=z0, scale=scale)
+                assert np.array_equal(got, want), (nsec, rate, T, NP, scale, "zi", np.abs(got - want).max())
                 assert np.abs(got - scipy.signal.sosfilt(sos, x, axis=0, zi=z0)[0] * scale).max() <= 1e-12
 
 
@@ -344,6 +380,26 @@ def check_stream_case(be, case, with_zi):
             assert np.array_equal(st.run(v, _capi.RM_F64), want)
         finally:
             _capi.check(be.lib, be.lib.rm_debug_set(be.ctx, b"stream_frames", 0), "rm_debug_set")
+
+
+def check_stream_sections(be, nsec, with_zi, case=STREAM_CASES[0]):
+    """rm_stream_push with a table of `nsec` sections (mixed_sos), cut three ways, bit for bit against the composition whose filter is
+    sos_restated: the state planes of that section count are stored and reloaded at every cut"""
+    H, W, L, S, dt = case
+    v = video(H, W, dt)
+    sos = mixed_sos(nsec, FPS, *BAND)
+    zi = sosfilt_zi(sos) if with_zi else None
+    f = as_read(be, v)
+    raw = composition(be, f, L, S, sos, zi, AMP)
+    want = f + raw
+    assert np.abs(raw).max() > 1e-3
+    with Stream(be, H, W, L, S, sos, zi) as st:
+        assert st.info() == (0, filtered_np(H, W, L, S), 16 * nsec * filtered_np(H, W, L, S))
+        for chunks in (None, (1,), CHUNKS):
+            got = st.run(v, _capi.RM_F64, chunks)
+            assert st.info()[0] == len(v)
+            assert np.array_equal(got, want), (nsec, with_zi, chunks, np.abs(got - want).max())
+            st.reset()
 
 
 def check_steady_start_is_quiet(be):

@@ -15,32 +15,7 @@ def emu():
     return Emu()
 
 
-class _EmuRoi:
-    """check_product's backend interface on the emulated C-ABI."""
-
-    def __init__(self, emu):
-        self.emu = emu
-        self.paths = set()
-
-    def dev(self, heat):
-        return heat
-
-    def roi(self, heat, clip, labelling):
-        roi = self.emu.heatmap_to_roi(heat, rr.THRESHOLD, clip_frame=clip, labelling=1 if labelling else 0)[0]
-        self.paths.add(self.emu.roi_path())
-        return roi
-
-    def rois(self, heat, H, W, K, min_area, clip):
-        return sc.heatmap_to_rois(self.emu.lib, self.emu.ctx, ptr(heat), H, W, K, min_area, threshold=rr.THRESHOLD, clip=clip)
-
-    def set(self, key, value):
-        self.emu.debug_set(key, value)
-
-    def stats(self):
-        return self.emu.contour_stats()
-
-    def path(self):
-        return self.emu.roi_path()
+_EmuRoi = rr.EmuRoi          # check_product's backend on this build (tests/roi_reference.py)
 
 
 @pytest.mark.parametrize("geometry", rr.GEOMETRIES + [(720, 1280)], ids=lambda g: "%dx%d" % g)

@@ -13,38 +13,7 @@ from tests import subjects_cases as sc
 pytestmark = pytest.mark.gpu
 
 
-class _GpuRoi:
-    """check_product's backend interface on the product's C-ABI (device heat maps)."""
-
-    def __init__(self):
-        import torch
-        assert torch.cuda.is_available()
-        from respmon_amd import _capi, device, dist
-        self.torch, self.device, self.dist = torch, device, dist
-        self.lib, self.ctx = _capi.load(), device.ctx()
-        self.paths = set()
-
-    def dev(self, heat):
-        return self.torch.from_numpy(np.ascontiguousarray(heat)).cuda()
-
-    def roi(self, heat, clip, labelling):
-        roi = self.dist.hip_heatmap_to_roi(heat, rr.THRESHOLD, clip_frame=clip, labelling=bool(labelling))
-        self.paths.add(self.dist.roi_path())
-        return roi
-
-    def rois(self, heat, H, W, K, min_area, clip):
-        return sc.heatmap_to_rois(self.lib, self.ctx, ctypes.c_void_p(heat.data_ptr()), H, W, K, min_area, threshold=rr.THRESHOLD, clip=clip,
-                                  stream=self.device.stream_ptr())
-
-    def set(self, key, value):
-        self.device.debug_set(key, value)
-
-    def stats(self):
-        n, labelled = self.dist.contour_stats()
-        return n, int(labelled)
-
-    def path(self):
-        return self.dist.roi_path()
+_GpuRoi = rr.GpuRoi          # check_product's backend on this build (tests/roi_reference.py)
 
 
 @pytest.fixture(scope="module")
